@@ -1,7 +1,12 @@
 """Benchmark of the DISORT flux hot path on MI355X (driver contract).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c5|c1|c3|c3l] [--planck]
-                    [--ncol C] [--ngpoint G]
+                    [--ncol C] [--ngpoint G] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line; ``--full`` adds
+the legs that take runs of their own (listed below).  ``--dump-outputs DIR`` writes
+what the last timed step returned, DIR/band_flux.npy: the band flux (C, L+1, 2),
+float64 (inputs are seeded, so equal arguments give equal inputs in every run).
 
 Default workload (BASELINE.json configs[3], SURVEY.md 8(d) "C4 GCM", the
 configuration the metric is quoted on): 1e4 synthetic columns x 64 g-points,
@@ -28,9 +33,14 @@ problem -> "scaling": "strong").
 Printed (rank 0): one JSON line with the contract fields plus
   roofline      dominant kernel (the layer-setup kernel), algorithmic FLOP per
                 launch / average launch time from HIP events on the solve stream
+                of the timed steps (with --graph: one eager step more, --full only)
+and, with ``--full`` at N=1 (null otherwise; each takes solves of its own after the
+timed region):
   cpu_baseline  oracle/ C restatement (a port of the DISORT algorithm, not
-                cdisort, which is absent) timed on the host cores, N=1 only
+                cdisort, which is absent) timed on the host cores
   max_rel_err   GPU vs that CPU restatement on a subsample of the workload
+  band_fused_vs_unfused_max_rel  the timed band flux vs hd_band_flux over per-g fluxes
+  unfused, end_to_end, end_to_end_band  extra_legs() below
 """
 
 from __future__ import annotations
@@ -351,6 +361,26 @@ def extra_legs(disort, prop, bc, temf, wts, steps, dev):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(directory, band, seed=20250217):
+    """--dump-outputs: the band flux (ncol, nlyr+1, 2) the last timed step returned, as
+    DIR/band_flux.npy (float64).  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the
+    columns is written, its (sorted) column indices beside it in
+    band_flux_columns.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    out = band.detach().cpu().numpy().astype(np.float64, copy=False)
+    per_col = out[0].nbytes + 8
+    room = DUMP_LIMIT_BYTES - 4096  # the two .npy headers
+    if out.nbytes > room:
+        keep = room // per_col
+        cols = np.sort(np.random.default_rng(seed).choice(out.shape[0], keep, replace=False))
+        out = out[cols]
+        np.save(os.path.join(directory, "band_flux_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(directory, "band_flux.npy"), np.ascontiguousarray(out))
+
+
 def launch_mode(gpus: int, env) -> str:
     """How this invocation runs (the driver's contract: ``bench.py --gpus N`` alone,
     or under ``torch.distributed.run`` with N ranks):
@@ -447,16 +477,26 @@ def main():
     ap.add_argument("--nlyr", type=int, default=None)
     ap.add_argument("--nstr", type=int, default=None)
     ap.add_argument("--planck", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline and the parity "
+                         "check against it, the fused-vs-unfused check, the unfused and "
+                         "host-array (end-to-end) legs and, with --graph, the eager step "
+                         "that times the kernels")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's band flux to DIR/band_flux.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the parity check against it")
     ap.add_argument("--chunk", type=int, default=0,
                     help="max solves per internal chunk (hd_context_set_chunk; 0 = auto)")
     ap.add_argument("--no-fuse", action="store_true",
                     help="unfused epilogue: per-g fluxes stored by hd_solve, then hd_band_flux")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the unfused and host-array (end-to-end) legs")
+                    help="with --full: skip the unfused and host-array (end-to-end) legs")
     ap.add_argument("--graph", action="store_true",
                     help="replay the solve + band sum as one captured HIP graph per step")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps {args.steps} must be >= 1")
     mode = launch_mode(args.gpus, os.environ)
     if mode == "spawn":
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -584,8 +624,12 @@ def main():
     elapsed = time.perf_counter() - t0
     tm = ctx.timing()
     ctx.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, band)
     timing_note = "HIP events on the solve stream over the timed steps"
-    if graph is not None:  # replays carry no timing events: one eager step for the kernels
+    kernel_timing = graph is None or args.full
+    # replays carry no timing events: with --full, one eager step for the kernels
+    if graph is not None and args.full:
         torch.cuda.synchronize()
         ctx.set_timing(True)
         solve()
@@ -617,7 +661,7 @@ def main():
         # dominant kernel roofline (the layer-setup kernel), per launch
         k1_avg_ms = tm.layer_ms / max(tm.layer_launches, 1)
         solves_per_launch = W * ncol * steps_timed / max(tm.layer_launches, 1)
-        ach = k1_flop * solves_per_launch / (k1_avg_ms * 1e-3) / 1e12
+        ach = k1_flop * solves_per_launch / (k1_avg_ms * 1e-3) / 1e12 if kernel_timing else 0.0
         pmc = load_pmc(nstr, nlyr, args.planck)
         traffic = None
         path_bytes = None
@@ -656,10 +700,15 @@ def main():
                  "layer_ms_per_step": round(tm.layer_ms / steps_timed, 3),
                  "sweep_ms_per_step": round(tm.sweep_ms / steps_timed, 3),
                  "timing": timing_note}
+        if not kernel_timing:  # graph replays carry no kernel events (--full takes them)
+            roofline = None
+            whole.update(layer_ms_per_step=None, sweep_ms_per_step=None,
+                         timing="none: --graph without --full")
         cpu = None
         max_err = None
         fused_vs_unfused = None
-        if fuse and world == 1:
+        full = args.full and world == 1
+        if fuse and full:
             # per-g fluxes (untimed) for the parity checks, from the timed step's own
             # kernel schedule (hd_solve_band with the per-point fluxes kept: bitwise
             # hd_solve's, tests/test_gpu_band.py), so that a rocprofv3 trace of this
@@ -672,9 +721,9 @@ def main():
             fused_vs_unfused = float(((band_fused - bunf).abs().max() /
                                       bunf.abs().max()).item())
         extra = None
-        if world == 1 and not args.no_extra:
+        if full and not args.no_extra:
             extra = extra_legs(disort, prop, bc, temf, wts, args.steps, dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             cpu, ref, n = cpu_baseline(prop, bc, temf, nstr, args.planck, wl, wu)
             m = ref.shape[0]
             got = flux[:m].cpu().numpy().reshape(-1, nlyr + 1, 2)[:n]

@@ -9,6 +9,8 @@
 #                        ab_libs/libhdisort_ab.so: build it first, scripts/ab/build_variant.sh ab)
 #   smoke                __graft_entry__.smoke()
 #   bench=NAME[:ARGS]    python bench.py ARGS              > bench_NAME.json
+#                        (ARGS --full: with the CPU baseline, parity and extra legs,
+#                        as the lines kept under profiles/ were taken)
 #   stats=NAME[:ARGS]    rocprofv3 --kernel-trace --stats of bench.py ARGS:
 #                        stats_NAME/ (kernel_stats.csv, kernel_trace.csv) + bench line
 #   pmc=NAME[:NSTR]      FETCH_SIZE and WRITE_SIZE passes (one --pmc pass each) over

@@ -27,8 +27,8 @@ def main():
     r = rows[0]
     calls, avg = int(r["Calls"]), float(r["AverageNs"]) * 1e-9
     # solves per launch from the line itself (achieved x its average launch / FLOP per
-    # solve): the stats file also holds the launches of the line's extra legs
-    # (unfused, end-to-end), so calls / steps does not give it
+    # solve): the stats file of a bench.py --full run also holds the launches of the
+    # line's extra legs (unfused, end-to-end), so calls / steps does not give it
     per_launch = round(rf["achieved"] * 1e12 * rf["avg_launch_ms"] * 1e-3 / rf["flop_per_solve"])
     launches_per_step = round(solves / per_launch)
     frac = rf["flop_per_solve"] * per_launch / avg / PEAK
