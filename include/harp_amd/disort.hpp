@@ -50,6 +50,16 @@ constexpr int ISS = 1;  // single-scattering albedo
 constexpr int IPM = 2;  // phase moments chi_1..chi_nmom
 constexpr int IUP = 0;  // upward flux
 constexpr int IDN = 1;  // downward flux (rfldir + rfldn)
+// forward_flx's record, flx[..., k]: cdisort's disort_radiant order (hdisort.h HD_FLX_*)
+constexpr int IRFLDIR = HD_FLX_RFLDIR;  // direct beam, unscaled depth
+constexpr int IRFLDN = HD_FLX_RFLDN;    // diffuse downward flux
+constexpr int IFLUP = HD_FLX_FLUP;      // upward flux
+constexpr int IDFDT = HD_FLX_DFDT;      // flux divergence (1 - ssa) 4 pi (uavg - B)
+constexpr int IUAVG = HD_FLX_UAVG;      // mean intensity
+constexpr int IUAVGDN = HD_FLX_UAVGDN;
+constexpr int IUAVGUP = HD_FLX_UAVGUP;
+constexpr int IUAVGSO = HD_FLX_UAVGSO;
+constexpr int NFLX = HD_NFLX;
 }  // namespace index
 
 #define HARP_AMD_ARG(T, name)                                         \
@@ -272,6 +282,23 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     return x.in_dev.is_cuda() ? flux : flux.to(x.in_dev);
   }
 
+  //! DISORT's full flux record (nwave, ncol, nlyr+1, index::NFLX) at the layer
+  //! boundaries, level 0 = surface: rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup,
+  //! uavgso (hd_solve_flx).  CPU tensors are staged on the device with torch copies.
+  torch::Tensor forward_flx(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
+                            torch::Tensor temf = torch::Tensor()) {
+    TORCH_CHECK(!usrtau_, "Disort.forward_flx: the flux record is at the layer boundaries "
+                          "(clear the 'usrtau' flag)");
+    TORCH_CHECK(onlyfl_, "Disort.forward_flx: a flux-only path (set the 'onlyfl' flag)");
+    Batch x = prepare(prop, bc, temf, /*stage=*/true);
+    auto flx = torch::empty({x.nwave, x.ncol, x.nlyr + 1, index::NFLX}, x.f64);
+    auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
+    const int rc = hd_solve_flx(context(x.dev.index()), &x.cfg, &x.in, flx.data_ptr<double>(),
+                                nullptr, reinterpret_cast<void*>(stream));
+    TORCH_CHECK(rc == HD_OK, "DisortWrapper::Run failed: ", hd_last_error(context(x.dev.index())));
+    return x.in_dev.is_cuda() ? flx : flx.to(x.in_dev);
+  }
+
   //! band flux (ncol, nlyr+1, 2) = sum_w weights[w] flux[w] with the sum fused into
   //! the solve (hd_solve_band): what examples/amars_lw.cpp:84-88 forms from
   //! forward's result, without storing the per-point fluxes
@@ -320,8 +347,9 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     }
   };
 
+  // stage: CPU tensors go to the device (entry points without a host-array twin)
   Batch prepare(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
-                torch::Tensor temf) {
+                torch::Tensor temf, bool stage = false) {
     TORCH_CHECK(prop.dim() == 4, "Disort.forward: prop must be (nwave, ncol, nlyr, nprop)");
     Batch x;
     x.nwave = prop.size(0);
@@ -341,7 +369,7 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     // pydisort's callers hand over CPU tensors (amars_sw.cpp:280, amars_lw.cpp:80,
     // radiation_band.cpp:124-127): on the flux path they go to the host-array entry
     // points, which copy them over in pieces beside the solve
-    x.host = !x.in_dev.is_cuda() && !radiance_;
+    x.host = !x.in_dev.is_cuda() && !radiance_ && !stage;
     x.f64 = torch::TensorOptions().dtype(torch::kFloat64).device(x.host ? x.in_dev : x.dev);
     auto to_dev = [&](torch::Tensor t) { return t.to(x.f64).contiguous(); };
     x.p = to_dev(prop);

@@ -59,7 +59,9 @@ extern "C" {
 
 /* Flags of the pydisort flag string (bindings): lamber
  * (required), onlyfl, planck, usrtau, usrang, intensity_correction +
- * old_intensity_correction, quiet, print-* are honoured; ibcnd is refused as
+ * old_intensity_correction, quiet, print-* are honoured (the full flux record of
+ * hd_solve_flx -- cdisort's rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup, uavgso
+ * at the layer boundaries -- with onlyfl and without usrtau); ibcnd is refused as
  * harp's driver refuses it (src/rtsolver/rt_solver_disort.cpp_:67-68), and so
  * are spher, general_source, output_uum and the new intensity correction
  * (not implemented); unknown names are refused. */
@@ -151,6 +153,39 @@ long hd_chunk_solves(const hd_config *cfg, long nsolve);
  */
 int hd_solve(hd_context *ctx, const hd_config *cfg, const hd_inputs *in, double *flux,
              int *status, void *stream);
+
+/*
+ * The full flux record of DISORT's c_fluxes at every level, in the
+ * component order of cdisort's disort_radiant struct:
+ *   flx  DEVICE [nwave][ncol][nlyr+1][HD_NFLX] f64, 16-byte aligned, level 0 = surface
+ *   HD_FLX_FLUP    upward flux (hd_solve's slot 0)
+ *   HD_FLX_RFLDIR  direct beam  mu0 F0 exp(-tau/mu0),  tau the UNSCALED cumulative
+ *                  optical depth from the top (sum of prop[..][0]); 0 without a beam
+ *   HD_FLX_RFLDN   diffuse downward flux: hd_solve's slot 1 (rfldir + rfldn) minus
+ *                  rfldir; not clamped (it may come out as -1e-17)
+ *   HD_FLX_UAVGUP  1/2 sum_i w_i I+_i   (upward hemisphere's share of the mean intensity)
+ *   HD_FLX_UAVGDN  1/2 sum_i w_i I-_i   (diffuse, delta-M scaled)
+ *   HD_FLX_UAVGSO  F0 exp(-tau'/mu0) / (4 pi),  tau' the delta-M SCALED depth
+ *   HD_FLX_UAVG    uavgup + uavgdn + uavgso  (mean intensity; actinic flux = 4 pi uavg)
+ *   HD_FLX_DFDT    (1 - ssa_in) 4 pi (uavg - B_lev), the flux divergence d(net flux)/
+ *                  d(tau): ssa_in is the INPUT single-scattering albedo (no dither, no
+ *                  delta-M scaling) of the layer directly above the level -- level
+ *                  lev < nlyr: layer lev; the top level nlyr: layer nlyr-1 (cdisort's
+ *                  layru for a depth on a layer boundary); B_lev the Planck band value
+ *                  at the level, 0 without HD_FLAG_PLANCK
+ * w_i, I+-_i: the double-Gauss weights and the azimuthally averaged intensities at the
+ * quadrature angles.  The solve is hd_solve's (same layer setup, adding sweep and
+ * chunking; flup and rfldir + rfldn agree with hd_solve's two slots to rounding).
+ * status / stream / return codes / ordering on the context as hd_solve.  Under stream
+ * capture the call never allocates: its scratch is larger than hd_solve's (wider
+ * back-substitution records) and hd_context_reserve does not size it, so a captured
+ * call returns HD_EINVAL unless an identical call outside capture came first.
+ */
+#define HD_NFLX 8
+enum { HD_FLX_RFLDIR = 0, HD_FLX_RFLDN, HD_FLX_FLUP, HD_FLX_DFDT,
+       HD_FLX_UAVG, HD_FLX_UAVGDN, HD_FLX_UAVGUP, HD_FLX_UAVGSO };
+int hd_solve_flx(hd_context *ctx, const hd_config *cfg, const hd_inputs *in, double *flx,
+                 int *status, void *stream);
 
 /*
  * Fused band epilogue: the solve of hd_solve plus the

@@ -7,6 +7,8 @@ hand-written HIP kernels for gfx950 (libhdisort.so, C-ABI include/hdisort.h).
 """
 
 from .index import IDN, IEX, IPM, ISS, IUP  # noqa: F401
+from .index import (IDFDT, IFLUP, IRFLDIR, IRFLDN, IUAVG, IUAVGDN, IUAVGSO,  # noqa: F401
+                    IUAVGUP, NFLX)
 from .rtsolver import RTSolver  # noqa: F401
 from .disort import Disort, DisortOptions, night_side_beam  # noqa: F401
 from .layer2level import Layer2LevelOptions, layer2level  # noqa: F401
@@ -14,4 +16,5 @@ from .scattering import PhaseMomentOptions, scattering_moments  # noqa: F401
 
 __all__ = ["Disort", "DisortOptions", "RTSolver", "layer2level", "Layer2LevelOptions",
            "IEX", "ISS", "IPM", "IUP", "IDN", "PhaseMomentOptions",
-           "scattering_moments", "night_side_beam"]
+           "scattering_moments", "night_side_beam", "IRFLDIR", "IRFLDN", "IFLUP", "IDFDT",
+           "IUAVG", "IUAVGDN", "IUAVGUP", "IUAVGSO", "NFLX"]

@@ -26,7 +26,7 @@ HD_STATUS_ERROR_MASK = 0x0F
 EXPORTED = ("hd_version", "hd_last_error", "hd_context_create", "hd_context_destroy",
             "hd_context_set_chunk", "hd_context_set_timing", "hd_context_set_max_sweeps",
             "hd_context_get_timing",
-            "hd_context_reserve", "hd_solve", "hd_solve_band", "hd_solve_host",
+            "hd_context_reserve", "hd_solve", "hd_solve_flx", "hd_solve_band", "hd_solve_host",
             "hd_solve_band_host", "hd_solve_radiance", "hd_quadrature", "hd_chunk_solves")
 
 # every symbol include/hdharp.h declares (harp-side steps around the solve)
@@ -113,6 +113,7 @@ def load(path: str = LIB_PATH):
     lib.hd_chunk_solves.argtypes = [ctypes.POINTER(HdConfig), ctypes.c_long]
     lib.hd_solve.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig), ctypes.POINTER(HdInputs),
                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.hd_solve_flx.argtypes = lib.hd_solve.argtypes
     lib.hd_solve_band.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                   ctypes.POINTER(HdInputs), ctypes.POINTER(HdBand),
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -210,6 +211,14 @@ class Context:
         rc = load().hd_solve(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
                              ctypes.c_void_p(flux_ptr), ctypes.c_void_p(status_ptr or 0),
                              ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def solve_flx(self, cfg: HdConfig, inp: HdInputs, flx_ptr: int, status_ptr: int | None,
+                  stream_ptr: int | None):
+        """hd_solve_flx: the eight-component flux record per level into flx_ptr."""
+        rc = load().hd_solve_flx(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                 ctypes.c_void_p(flx_ptr), ctypes.c_void_p(status_ptr or 0),
+                                 ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
     def solve_band(self, cfg: HdConfig, inp: HdInputs, band: HdBand, flux_ptr: int | None,

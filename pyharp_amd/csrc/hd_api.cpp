@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -389,24 +390,26 @@ int leave(hd_context* ctx, hipStream_t stream, bool capturing) {
   return HD_OK;
 }
 
-int validate(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, const double* flux) {
-  if (!cfg || !in) return fail(ctx, HD_EINVAL, "hd_solve: null config/inputs");
+// who: the name of the entry point in the messages
+int validate(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, const double* flux,
+             const char* who = "hd_solve") {
+  if (!cfg || !in) return fail(ctx, HD_EINVAL, "%s: null config/inputs", who);
   if (cfg->nstr < 2 || cfg->nstr % 2 || cfg->nstr / 2 > hd::kMaxNN)
-    return fail(ctx, HD_EINVAL, "hd_solve: nstr=%d must be even and in [2, %d]", cfg->nstr,
+    return fail(ctx, HD_EINVAL, "%s: nstr=%d must be even and in [2, %d]", who, cfg->nstr,
                 2 * hd::kMaxNN);
-  if (cfg->nlyr < 1) return fail(ctx, HD_EINVAL, "hd_solve: nlyr=%d < 1", cfg->nlyr);
-  if (cfg->nprop < 1) return fail(ctx, HD_EINVAL, "hd_solve: nprop=%d < 1", cfg->nprop);
-  if (cfg->nmom < 0) return fail(ctx, HD_EINVAL, "hd_solve: nmom=%d < 0", cfg->nmom);
+  if (cfg->nlyr < 1) return fail(ctx, HD_EINVAL, "%s: nlyr=%d < 1", who, cfg->nlyr);
+  if (cfg->nprop < 1) return fail(ctx, HD_EINVAL, "%s: nprop=%d < 1", who, cfg->nprop);
+  if (cfg->nmom < 0) return fail(ctx, HD_EINVAL, "%s: nmom=%d < 0", who, cfg->nmom);
   if (cfg->flags & ~(HD_FLAG_LAMBER | HD_FLAG_PLANCK | HD_FLAG_ONLYFL))
-    return fail(ctx, HD_EINVAL, "hd_solve: unsupported flags 0x%x", cfg->flags);
+    return fail(ctx, HD_EINVAL, "%s: unsupported flags 0x%x", who, cfg->flags);
   if (in->nwave < 0 || in->ncol < 0)
-    return fail(ctx, HD_EINVAL, "hd_solve: negative nwave/ncol");
+    return fail(ctx, HD_EINVAL, "%s: negative nwave/ncol", who);
   if ((long)in->nwave * in->ncol > 0 && (!in->prop || !flux))
-    return fail(ctx, HD_EINVAL, "hd_solve: prop and flux are required");
+    return fail(ctx, HD_EINVAL, "%s: prop and flux are required", who);
   if ((cfg->flags & HD_FLAG_PLANCK) && (!in->temf || !in->wave_lower || !in->wave_upper))
-    return fail(ctx, HD_EINVAL, "hd_solve: planck needs temf, wave_lower, wave_upper");
+    return fail(ctx, HD_EINVAL, "%s: planck needs temf, wave_lower, wave_upper", who);
   if ((long)in->nwave * in->ncol > (long)0x7fffffff)
-    return fail(ctx, HD_EINVAL, "hd_solve: nwave*ncol exceeds 2^31");
+    return fail(ctx, HD_EINVAL, "%s: nwave*ncol exceeds 2^31", who);
   return HD_OK;
 }
 
@@ -615,9 +618,15 @@ int hd_quadrature(int nstr, double* mu, double* w) {
 namespace {
 
 // hd_solve's enqueue body: everything it launches ends on `stream` (the side
-// and lay streams fork from it and join back into it)
+// and lay streams fork from it and join back into it).
+// flx (hd_solve_flx; flux and band null): the same chunks and streams with the flx
+// instantiations -- register path hd_layer_kernel -> hd_sweep_flx_kernel ->
+// hd_backsub_flx_kernel / _tail_kernel (never the NN-lane, LDS-state or column sweeps),
+// team path hd_team_mfma_layer_kernel -> hd_team_mfma_sweep_flx_kernel -- over the wider
+// back-substitution records, plus the per-level prologue hd_flx_level_kernel, whose
+// output only the sweep (surface level) and the back-substitution read.
 int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
-                  const hd_band* band, int*& status, hipStream_t stream) {
+                  const hd_band* band, int*& status, hipStream_t stream, double* flx = nullptr) {
   int rc = HD_OK;
   const long nsolve = (long)in->nwave * in->ncol;
   const int nn = cfg->nstr / 2;
@@ -629,8 +638,12 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
 
   long chunk = ctx->chunk > 0 ? std::min(ctx->chunk, nsolve) : auto_chunk(nsolve, nn, nlyr, planck);
   const size_t ne1 = hd::layer_record_doubles(nn);
-  const size_t ne2 = hd::bsub_record_doubles(nn);
-  const size_t per = hd::scratch_doubles_per_solve(nn, nlyr, planck);
+  const size_t ne2 = flx ? hd::bsub_flx_record_doubles(nn) : hd::bsub_record_doubles(nn);
+  const int nb = 2;  // buffers of the per-chunk regions (two chunks in flight)
+  // hd_solve_flx: the wider records and the per-level terms [3][nlyr+1], per buffer
+  const size_t per = hd::scratch_doubles_per_solve(nn, nlyr, planck) +
+                     (flx ? nb * ((ne2 - hd::bsub_record_doubles(nn)) * nlyr + 3 * (size_t)(nlyr + 1))
+                          : 0);
   // fused band epilogue: register path -- column-major chunks, the surface
   // fluxes of two chunks in flight [2][2][chunk] and one chunk's run partials
   // [wave][nslot][lev][2]; team path -- one chunk's fluxes when the caller
@@ -659,7 +672,7 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   // the caller's stream (prologue, layer kernel, sweep, tail back-substitution),
   // without the fork/join of the three-stream pipeline below (C1/C3 latency)
   // nstr 16 by the column kernel: every chunk wholly on the caller's stream
-  const bool col = reg && nn == 8 && ctx->column;
+  const bool col = reg && nn == 8 && ctx->column && !flx;
   const bool single = reg && !col && nsolve <= chunk;
   // team path with several chunks: chunk k+1's prologue and layer kernel on the
   // `lay` stream beside chunk k's sweep on the caller's stream
@@ -676,8 +689,8 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   // and thermal terms and the prologue stays.
   const bool beam_in_sweep = beam && !planck;
   const bool need_tauc = beam && !beam_in_sweep;
-  const bool need_pro = planck || need_tauc;
-  const int nb = 2;  // buffers of the per-chunk regions (two chunks in flight)
+  const bool need_pro = planck || need_tauc;  // prologue output the layer kernel reads
+  const bool any_pro = need_pro || flx;       // ... or the sweep / back-substitution
   // Scratch regions, sized for the largest chunk so that no region moves between
   // chunks (inside a region the kernels interleave with the chunk's own nsc):
   //   layer ops[nb] | bsub[nb] | xsurf[nb] | planck[nb] | tauc[nb]
@@ -690,6 +703,7 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   double* xsurf_b[2];
   double* planck_b[2];
   double* tauc_b[2];
+  double* lvl_b[2] = {nullptr, nullptr};  // hd_solve_flx: per-level terms
   double* band_q = nullptr;  // band-epilogue scratch after the regions
   {
     double* q = ctx->scratch;
@@ -701,6 +715,8 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
       if (planck) q += (size_t)(nlyr + 3) * chunk;
     }
     for (int b = 0; b < nb; ++b, q += (size_t)nlyr * chunk) tauc_b[b] = q;
+    if (flx)
+      for (int b = 0; b < nb; ++b, q += 3 * (size_t)(nlyr + 1) * chunk) lvl_b[b] = q;
     band_q = q;
   }
   double* fsurf_b[2] = {nullptr, nullptr};
@@ -757,6 +773,22 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
     pa.nwave = in->nwave;
   };
 
+  // hd_solve_flx: the chunk's per-level prologue, beside its tauc / planck one
+  auto flx_level = [&](long s0, int nsc, int b, hipStream_t st) {
+    if (!flx) return hipSuccess;
+    hd::FlxLevelArgs fa{};
+    fa.prop = in->prop;
+    fa.fbeam = in->fbeam;
+    fa.umu0 = in->umu0;
+    fa.out = lvl_b[b];
+    fa.s0 = s0;
+    fa.nsc = nsc;
+    fa.nlyr = nlyr;
+    fa.nprop = cfg->nprop;
+    fa.use_f = nm >= cfg->nstr;
+    fa.f_slot = 1 + cfg->nstr;
+    return hd::launch_flx_level(fa, st);
+  };
   if ((reg && !single && !col) || team_pipe) {
     // fork: the side stream sees everything the caller's stream did before this
     // call (the inputs) -- and, under stream capture, joins the graph here
@@ -775,10 +807,13 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
       // buffer `buf` is free once sweep k-2 (its last reader) is done
       if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_sweep[buf], 0));
       hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, ctx->lay);
+      HD_HIP(ctx, flx_level(s0, nsc, buf, ctx->lay));
     } else if (!reg || single || col) {
       hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, stream);
-    } else if (k == 0 && need_pro) {
+      HD_HIP(ctx, flx_level(s0, nsc, buf, stream));
+    } else if (k == 0 && any_pro) {
       hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, ctx->side);
+      HD_HIP(ctx, flx_level(s0, nsc, buf, ctx->side));
       HD_HIP(ctx, hipEventRecord(ctx->ev_pro[0], ctx->side));
     }
     hd::LayerArgs la{};
@@ -826,6 +861,9 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
     sa.lean = ctx->lean;
     sa.quad = ctx->quad;
     sa.lean8 = ctx->lean8;
+    hd::FlxArgs fx{};
+    fx.flx = flx;
+    fx.lvl = lvl_b[buf];
     if (band && reg) {
       sa.wts = band->weight;
       sa.part = part;
@@ -863,9 +901,12 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
       e = hd::launch_layer_nn(nn, la, stream);
       if (ev) HD_HIP(ctx, hipEventRecord(ev[1], stream));
       if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-      if (e == hipSuccess) e = hd::launch_sweep_nn(nn, sa, stream);
+      if (e == hipSuccess)
+        e = flx ? hd::launch_sweep_flx_nn(nn, sa, fx, stream) : hd::launch_sweep_nn(nn, sa, stream);
       if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-      if (e == hipSuccess) e = hd::launch_backsub_nn(nn, sa, stream, true);
+      if (e == hipSuccess)
+        e = flx ? hd::launch_backsub_flx_nn(nn, sa, fx, stream, true)
+                : hd::launch_backsub_nn(nn, sa, stream, true);
       if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), stream);
     } else if (reg) {
       // layer kernel k on `lay`: its inputs (prologue k) are in, and sweep k-2,
@@ -881,8 +922,10 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
       if (e == hipSuccess) {
         HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
         if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
+        // hd_solve_flx without a prologue the layer kernel waited for: the sweep reads it
+        if (flx && !need_pro) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_pro[buf], 0));
         if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-        e = hd::launch_sweep_nn(nn, sa, stream);
+        e = flx ? hd::launch_sweep_flx_nn(nn, sa, fx, stream) : hd::launch_sweep_nn(nn, sa, stream);
         if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
       }
     } else if (team_pipe) {
@@ -895,7 +938,8 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
         // the chunk flux buffer[buf] is free once band reduce k-2 (its reader) is done
         if (band && k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
         if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-        e = hd::launch_team_sweep_nn(nn, sa, stream);
+        e = flx ? hd::launch_team_sweep_flx_nn(nn, sa, fx, stream)
+                : hd::launch_team_sweep_nn(nn, sa, stream);
         if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
       }
       HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
@@ -908,21 +952,31 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
         e = hd::launch_band_reduce(band_args(s0, nsc, buf), ctx->side);
         HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], ctx->side));
       }
+    } else if (flx) {  // team path, one chunk
+      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], stream));
+      e = hd::launch_team_layer_nn(nn, la, stream);
+      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], stream));
+      if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
+      if (e == hipSuccess) e = hd::launch_team_sweep_flx_nn(nn, sa, fx, stream);
+      if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
     } else {
       e = hd::launch_solve_chunk_team(nn, nullptr, nullptr, la, sa, stream, ev);
       if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), stream);
     }
-    if (e != hipSuccess) return fail(ctx, HD_EHIP, "hd_solve: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess)
+      return fail(ctx, HD_EHIP, "%s: launch failed: %s", flx ? "hd_solve_flx" : "hd_solve",
+                  hipGetErrorString(e));
     if (reg && !single && !col) {
       HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
       // next chunk's prologue into the other buffer (free: the side stream already
       // waited for the sweep of chunk k-1, the last user of that buffer)
       const long s1 = s0 + chunk;
-      if (s1 < nsolve && need_pro) {
+      if (s1 < nsolve && any_pro) {
         hd::TaucArgs ta1;
         hd::PlanckArgs pa1;
         prologue_args(s1, (int)std::min(chunk, nsolve - s1), buf ^ 1, ta1, pa1);
         hd::launch_prologue(planck ? &pa1 : nullptr, need_tauc ? &ta1 : nullptr, ctx->side);
+        HD_HIP(ctx, flx_level(s1, (int)std::min(chunk, nsolve - s1), buf ^ 1, ctx->side));
         HD_HIP(ctx, hipEventRecord(ctx->ev_pro[buf ^ 1], ctx->side));
       }
       HD_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_sweep[buf], 0));
@@ -934,11 +988,12 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
       // (160 000, 3 chunks) 10.0 -> 10.3 M; with 5 and 10 chunks the capped kernel
       // hidden under the next layer kernel stays ahead (profiles/r02_tail_ab/)
       const bool tail = s1 >= nsolve || (nsolve + chunk - 1) / chunk <= 3;
-      e = hd::launch_backsub_nn(nn, sa, ctx->side, tail);
+      e = flx ? hd::launch_backsub_flx_nn(nn, sa, fx, ctx->side, tail)
+              : hd::launch_backsub_nn(nn, sa, ctx->side, tail);
       if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), ctx->side);
       if (e != hipSuccess)
-        return fail(ctx, HD_EHIP, "hd_solve: back-substitution launch failed: %s",
-                    hipGetErrorString(e));
+        return fail(ctx, HD_EHIP, "%s: back-substitution launch failed: %s",
+                    flx ? "hd_solve_flx" : "hd_solve", hipGetErrorString(e));
       HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], ctx->side));
     }
   }
@@ -995,6 +1050,20 @@ int hd_solve(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double*
   if ((long)in->nwave * in->ncol == 0) return HD_OK;
   return run_solve(ctx, status, stream, "hd_solve", [&](int*& st, hipStream_t s) {
     return solve_enqueue(ctx, cfg, in, flux, nullptr, st, s);
+  });
+}
+
+int hd_solve_flx(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flx,
+                 int* status, void* stream) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_flx: null context");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = validate(ctx, cfg, in, flx, "hd_solve_flx");
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  if (reinterpret_cast<uintptr_t>(flx) % 16)
+    return fail(ctx, HD_EINVAL, "hd_solve_flx: flx must be 16-byte aligned");
+  return run_solve(ctx, status, stream, "hd_solve_flx", [&](int*& st, hipStream_t s) {
+    return solve_enqueue(ctx, cfg, in, nullptr, nullptr, st, s, flx);
   });
 }
 

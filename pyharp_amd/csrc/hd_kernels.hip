@@ -24,6 +24,7 @@
 //   the vmcnt-ordered round trips of the one-wave-per-SIMD sweep)
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -43,6 +44,9 @@ struct QuadTables {
   Quad<8> q8;
 };
 __constant__ QuadTables c_quad;
+// hd_solve_flx: h = g / mu of every NN (row NN-1), the mean-intensity functional
+// sum_i w_i I_i = sum_i h_i psi_i -- a table of its own, so that Quad keeps its layout
+__constant__ double c_quad_h[kMaxRegNN][kMaxRegNN];
 // 1/n for the beam's Legendre recursion (uniform index: scalar loads)
 __constant__ double c_inv_int[2 * kMaxRegNN + 2] = {
     0.0,        1.0,        1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,  1.0 / 6,
@@ -127,6 +131,51 @@ __global__ __launch_bounds__(256) void hd_tauc_kernel(TaucArgs A) {
     const double f = A.use_f ? q[A.f_slot] : 0.0;
     A.out[(size_t)lc * A.nsc + sl] = tauc;
     tauc += (1.0 - a * f) * q[0];
+  }
+}
+
+// ============================================================================
+// K0c (hd_solve_flx): the terms of the flux record that need the input optics, per
+// solver level lc (0 = top): rfldir = mu0 F0 exp(-tau/mu0) on the UNSCALED depth,
+// uavgso = F0 exp(-tau'/mu0) / (4 pi) on the delta-M scaled one (hd_tauc_kernel's
+// sum), and (1 - ssa_in) 4 pi of the layer above the level (the top level: the top
+// layer; the input albedo, no dither, no scaling -- cdisort's layru at a boundary)
+// ============================================================================
+__global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
+  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= A.nsc) return;
+  const long s = A.s0 + sl;
+  const int L = A.nlyr, np = A.nprop;
+  const size_t nsc = A.nsc;
+  const double* p = A.prop + (size_t)s * L * np;
+  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
+  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
+  const bool beam = fb > 0.0 && mu0 > 0.0;
+  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  const double f0mu0 = beam ? fb * mu0 : 0.0;
+  const double f04pi = beam ? fb / (4.0 * kPi) : 0.0;
+  double* o_dir = A.out;
+  double* o_so = A.out + (size_t)(L + 1) * nsc;
+  double* o_abs = A.out + 2 * (size_t)(L + 1) * nsc;
+  double tau = 0.0, tauc = 0.0, absl = 0.0;
+  for (int lc = 0; lc <= L; ++lc) {  // solver order: top (harp layer L-1) first
+    if (lc < L) {
+      const double* q = p + (size_t)(L - 1 - lc) * np;
+      const double a_in = np > 1 ? q[1] : 0.0;
+      if (lc == 0) absl = (1.0 - a_in) * (4.0 * kPi);
+      o_dir[(size_t)lc * nsc + sl] = f0mu0 * exp(-tau * rmu0);
+      o_so[(size_t)lc * nsc + sl] = f04pi * exp(-tauc * rmu0);
+      o_abs[(size_t)lc * nsc + sl] = absl;
+      absl = (1.0 - a_in) * (4.0 * kPi);
+      const double a = a_in == 1.0 ? 1.0 - kDither : a_in;
+      const double f = A.use_f ? q[A.f_slot] : 0.0;
+      tau += q[0];
+      tauc += (1.0 - a * f) * q[0];
+    } else {
+      o_dir[(size_t)lc * nsc + sl] = f0mu0 * exp(-tau * rmu0);
+      o_so[(size_t)lc * nsc + sl] = f04pi * exp(-tauc * rmu0);
+      o_abs[(size_t)lc * nsc + sl] = absl;
+    }
   }
 }
 
@@ -654,13 +703,35 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
 // ============================================================================
 // K2: per-solve adding sweep + back-substitution
 // ============================================================================
+// hd_solve_flx: the eight components of solver level lc (harp level L - lc) of solve s
+// from the level's fluxes (up, total down), its two hemispheric mean intensities and
+// Planck value, and the prologue's per-level terms
+__device__ __forceinline__ void flx_emit(const FlxArgs& F, long s, long sl, size_t nsc, int L,
+                                         int lc, double up, double dn, double uavgup,
+                                         double uavgdn, double blev) {
+  const size_t nl = (size_t)(L + 1) * nsc;
+  const double rfldir = F.lvl[(size_t)lc * nsc + sl];
+  const double uavgso = F.lvl[nl + (size_t)lc * nsc + sl];
+  const double absl = F.lvl[2 * nl + (size_t)lc * nsc + sl];
+  const double uavg = uavgup + uavgdn + uavgso;
+  double* o = F.flx + ((size_t)s * (L + 1) + (L - lc)) * kNFlx;
+  double2* o2 = reinterpret_cast<double2*>(o);
+  o2[0] = make_double2(rfldir, dn - rfldir);
+  o2[1] = make_double2(up, absl * (uavg - blev));
+  o2[2] = make_double2(uavg, uavgdn);
+  o2[3] = make_double2(uavgup, uavgso);
+}
+
 // The adding sweep of solve s (chunk lane sl): layer lc's record through
 // rec_at(lc), a callable returning a getter e -> RecL element e (hd_sweep_kernel:
 // loads from the HBM record; hd_column_kernel: the layer setup run right there
 // into registers).  Stores the back-substitution records, the surface level and
 // x; returns the status bits.
-template <int NN, bool NT, class RecAt>
-__device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, RecAt&& rec_at) {
+// FLX (hd_solve_flx): the records are RecBF -- each level also gets the mean-intensity
+// row rh and scalar ch -- and the surface level's eight components go to F->flx.
+template <int NN, bool NT, bool FLX = false, class RecAt>
+__device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, RecAt&& rec_at,
+                                          const FlxArgs* F = nullptr) {
   const Quad<NN>& Qc = quad<NN>();
   const int L = A.nlyr;
   const size_t nsc = A.nsc;
@@ -694,7 +765,7 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
 
   for (int lc = 0; lc < L; ++lc) {
     using RL = RecL<NN>;
-    using RB = RecB<NN>;
+    using RB = std::conditional_t<FLX, RecBF<NN>, RecB<NN>>;
     auto rec = rec_at(lc);
     PairOutT<NT> bp{reinterpret_cast<double2*>(A.bsub) + (size_t)lc * RB::pairs * nsc + sl, nsc, 0.0};
     // this layer's R~ (upper) and S~+ ; each record element is read once
@@ -728,6 +799,20 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
       bp.close(RB::Rc + NN - 1);
       bp.put(RB::Cs, fma(twopi, cs, f0mu0 * eb));
       bp.close(RB::Cs);
+    }
+    if constexpr (FLX) {  // the same level's sum_i w_i I-_i = rh . I+ + ch, h = g / mu
+      double ch = 0.0;
+#pragma unroll
+      for (int i = 0; i < NN; ++i) {
+        double t = 0.0;
+#pragma unroll
+        for (int j = 0; j < NN; ++j) t = fma(HD_SYM(ra, j, i), c_quad_h[NN - 1][j], t);
+        bp.put(RB::Rh + i, t);
+        ch = fma(c_quad_h[NN - 1][i], sd[i], ch);
+      }
+      bp.close(RB::Rh + NN - 1);
+      bp.put(RB::Ch, ch);
+      bp.close(RB::Ch);
     }
     HD_PHASE();
     // A = Ra (full); W1 = I - R_l A ; v1 = R_l Sd + S+
@@ -921,6 +1006,20 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
       A.fsurf[nsc + sl] = f1;
     }
     chk += f0 + f1;
+    if constexpr (FLX) {
+      double hu = 0.0, hd_ = 0.0;
+#pragma unroll
+      for (int i = 0; i < NN; ++i) {
+        const double h = c_quad_h[NN - 1][i];
+        hu = fma(h, ip[i], hu);
+        double t = sd[i];
+#pragma unroll
+        for (int j = 0; j < NN; ++j) t += HD_SYM(ra, i, j) * ip[j];
+        hd_ = fma(h, t, hd_);
+      }
+      const double bl = A.planck ? A.planckv[sl] : 0.0;  // B at harp level 0
+      flx_emit(*F, s, sl, nsc, L, L, f0, f1, 0.5 * hu, 0.5 * hd_, bl);
+    }
   }
   A.xsurf[sl] = x;
   if (!isfinite(chk)) st |= kStNonFinite;
@@ -945,8 +1044,27 @@ __global__ __launch_bounds__(64) void hd_sweep_kernel(SweepArgs A) {
   }
 }
 
-template <int NN, bool PRE, bool NT>
-__device__ __forceinline__ void backsub_body(const SweepArgs& A);
+// hd_solve_flx's sweep: hd_sweep_kernel with the second functional (RecBF records)
+template <int NN, bool NT>
+__global__ __launch_bounds__(64) void hd_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
+  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= A.nsc) return;
+  const long s = A.s0 + sl;
+  const size_t nsc = A.nsc;
+  auto rec_at = [&](int lc) {
+    const double2* lp =
+        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
+    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
+  };
+  const int st = sweep_body<NN, NT, true>(A, sl, s, rec_at, &F);
+  if (st) {
+    atomicOr(&A.status[s], st);
+    if (st & 0x0F) atomicOr(A.anyerr, 1);
+  }
+}
+
+template <int NN, bool PRE, bool NT, bool FLX = false>
+__device__ __forceinline__ void backsub_body(const SweepArgs& A, const FlxArgs* F = nullptr);
 
 #if HD_AB_VARIANTS
 // ============================================================================
@@ -1566,8 +1684,9 @@ __global__ __launch_bounds__(64) void hd_sweep_quad_kernel(SweepArgs A) {
 // The arithmetic of both back-substitution kernels (identical expression order,
 // so a solve's fluxes do not depend on which kernel ran its chunk).  PRE: the
 // next layer's record is loaded into registers before this layer is computed.
-template <int NN, bool PRE, bool NT>
-__device__ __forceinline__ void backsub_body(const SweepArgs& A) {
+// FLX (hd_solve_flx): RecBF records; every level's eight components go to F->flx.
+template <int NN, bool PRE, bool NT, bool FLX>
+__device__ __forceinline__ void backsub_body(const SweepArgs& A, const FlxArgs* F) {
   const Quad<NN>& Qc = quad<NN>();
   const long lane_sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = lane_sl < A.nsc;
@@ -1635,7 +1754,7 @@ __device__ __forceinline__ void backsub_body(const SweepArgs& A) {
   }
   // this layer's record through `get` (RecB element indices: ZT column-major, t,
   // rc, cs)
-  using RB = RecB<NN>;
+  using RB = std::conditional_t<FLX, RecBF<NN>, RecB<NN>>;
   auto layer = [&](int lc, auto&& get) {
     double nip[NN];
 #pragma unroll
@@ -1655,6 +1774,18 @@ __device__ __forceinline__ void backsub_body(const SweepArgs& A) {
     const int lev = L - lc;
     emit(lev, twopi * up, dn, true);
     chk += twopi * up + dn;
+    if constexpr (FLX) {
+      HD_PHASE();  // the level's second functional after its fluxes, not interleaved
+      double hu = 0.0, hd_ = get(RB::Ch);
+#pragma unroll
+      for (int i = 0; i < NN; ++i) {
+        hu = fma(c_quad_h[NN - 1][i], nip[i], hu);
+        hd_ = fma(get(RB::Rh + i), nip[i], hd_);
+      }
+      const double bl = A.planck ? A.planckv[(size_t)lev * nsc + sl] : 0.0;
+      flx_emit(*F, s, sl, nsc, L, lc, twopi * up, dn, 0.5 * hu, 0.5 * hd_, bl);
+      chk += hu + hd_;
+    }
   };
   auto rec_ptr = [&](int lc) {
     return reinterpret_cast<const double2*>(A.bsub) + (size_t)lc * RB::pairs * nsc + sl;
@@ -1711,6 +1842,21 @@ void hd_backsub_kernel(SweepArgs A) {
 template <int NN, bool NT>
 __global__ __launch_bounds__(64) void hd_backsub_tail_kernel(SweepArgs A) {
   backsub_body<NN, true, NT>(A);
+}
+
+// hd_solve_flx's back-substitutions: the same two kernels over RecBF records (two more
+// dot products and eight stores per level).  The one that runs beside the next chunk's
+// layer kernel has a cap of its own, four waves per SIMD (128 VGPRs; NN = 8: three,
+// 168): at hd_backsub_kernel's five it spilled (up to 68 B of scratch at NN 5, 6, 8),
+// and at four NN = 8 still did (20 B).
+template <int NN, bool NT>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NN == 8 ? 3 : 4)))
+void hd_backsub_flx_kernel(SweepArgs A, FlxArgs F) {
+  backsub_body<NN, false, NT, true>(A, &F);
+}
+template <int NN, bool NT>
+__global__ __launch_bounds__(64) void hd_backsub_flx_tail_kernel(SweepArgs A, FlxArgs F) {
+  backsub_body<NN, true, NT, true>(A, &F);
 }
 
 // ============================================================================
@@ -1890,6 +2036,11 @@ hipError_t upload_quad_tables(const QuadHost* per_nn /* [kMaxNN], index nn-1 */)
   fill_quad<6>(t.q6, per_nn[5]);
   fill_quad<7>(t.q7, per_nn[6]);
   fill_quad<8>(t.q8, per_nn[7]);
+  double h[kMaxRegNN][kMaxRegNN] = {};
+  for (int nn = 1; nn <= kMaxRegNN; ++nn)
+    for (int i = 0; i < nn; ++i) h[nn - 1][i] = per_nn[nn - 1].g[i] / per_nn[nn - 1].mu[i];
+  hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_quad_h), h, sizeof(h), 0, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return e;
   return hipMemcpyToSymbol(HIP_SYMBOL(c_quad), &t, sizeof(t), 0, hipMemcpyHostToDevice);
 }
 
@@ -1956,6 +2107,63 @@ static void launch_backsub(const SweepArgs& sa, hipStream_t stream, bool tail) {
   else if (tail) hipLaunchKernelGGL((hd_backsub_tail_kernel<NN, false>), gt, dim3(64), 0, stream, sa);
   else if (nt) hipLaunchKernelGGL((hd_backsub_kernel<NN, true>), gc, dim3(256), 0, stream, sa);
   else hipLaunchKernelGGL((hd_backsub_kernel<NN, false>), gc, dim3(256), 0, stream, sa);
+}
+
+hipError_t launch_flx_level(const FlxLevelArgs& fa, hipStream_t stream) {
+  hipLaunchKernelGGL(hd_flx_level_kernel, dim3((unsigned)((fa.nsc + 255) / 256)), dim3(256), 0,
+                     stream, fa);
+  return hipGetLastError();
+}
+
+template <int NN>
+static void launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
+  const dim3 g((unsigned)((sa.nsc + 63) / 64));
+  if (sa.nsc >= kNtMinSolves)
+    hipLaunchKernelGGL((hd_sweep_flx_kernel<NN, true>), g, dim3(64), 0, stream, sa, fx);
+  else
+    hipLaunchKernelGGL((hd_sweep_flx_kernel<NN, false>), g, dim3(64), 0, stream, sa, fx);
+}
+
+hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
+  switch (nn) {
+    case 1: launch_sweep_flx<1>(sa, fx, stream); break;
+    case 2: launch_sweep_flx<2>(sa, fx, stream); break;
+    case 3: launch_sweep_flx<3>(sa, fx, stream); break;
+    case 4: launch_sweep_flx<4>(sa, fx, stream); break;
+    case 5: launch_sweep_flx<5>(sa, fx, stream); break;
+    case 6: launch_sweep_flx<6>(sa, fx, stream); break;
+    case 7: launch_sweep_flx<7>(sa, fx, stream); break;
+    case 8: launch_sweep_flx<8>(sa, fx, stream); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+template <int NN>
+static void launch_backsub_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream,
+                               bool tail) {
+  const dim3 gt((unsigned)((sa.nsc + 63) / 64)), gc((unsigned)((sa.nsc + 255) / 256));
+  const bool nt = sa.nsc >= kNtMinSolves;
+  if (tail && nt) hipLaunchKernelGGL((hd_backsub_flx_tail_kernel<NN, true>), gt, dim3(64), 0, stream, sa, fx);
+  else if (tail) hipLaunchKernelGGL((hd_backsub_flx_tail_kernel<NN, false>), gt, dim3(64), 0, stream, sa, fx);
+  else if (nt) hipLaunchKernelGGL((hd_backsub_flx_kernel<NN, true>), gc, dim3(256), 0, stream, sa, fx);
+  else hipLaunchKernelGGL((hd_backsub_flx_kernel<NN, false>), gc, dim3(256), 0, stream, sa, fx);
+}
+
+hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
+                                 hipStream_t stream, bool tail) {
+  switch (nn) {
+    case 1: launch_backsub_flx<1>(sa, fx, stream, tail); break;
+    case 2: launch_backsub_flx<2>(sa, fx, stream, tail); break;
+    case 3: launch_backsub_flx<3>(sa, fx, stream, tail); break;
+    case 4: launch_backsub_flx<4>(sa, fx, stream, tail); break;
+    case 5: launch_backsub_flx<5>(sa, fx, stream, tail); break;
+    case 6: launch_backsub_flx<6>(sa, fx, stream, tail); break;
+    case 7: launch_backsub_flx<7>(sa, fx, stream, tail); break;
+    case 8: launch_backsub_flx<8>(sa, fx, stream, tail); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bool tail) {
@@ -2061,7 +2269,13 @@ size_t bsub_record_doubles(int nn) {
   return (size_t)((nn * nn + 2 * nn + 2) & ~1);
 }
 
+size_t bsub_flx_record_doubles(int nn) {
+  if (nn <= kMaxRegNN) return 2 * reg_pairs_b(nn) + (size_t)even_up(nn) + 2;
+  return (size_t)((nn * nn + 3 * nn + 3) & ~1);  // team: the rh row and ch after cs
+}
+
 static_assert(RecL<8>::pairs == 45 && RecB<8>::pairs == 41, "C4 record pairs");
+static_assert(RecBF<8>::pairs == 46 && RecBF<3>::pairs == RecB<3>::pairs + 3, "flx record pairs");
 
 size_t scratch_doubles_per_solve(int nn, int nlyr, bool planck) {
   // every per-chunk region is double-buffered: chunk k+1's layer kernel (and its

@@ -44,6 +44,20 @@ struct RecB {  // back-substitution record: ZT (column-major) | t | rc | cs
   static constexpr int Cs = Rc + even_up(NN);
   static constexpr int pairs = (Cs + 2) / 2;
 };
+// hd_solve_flx's back-substitution record: RecB's elements where RecB has them,
+// then the mean-intensity functional of the same level -- rh_i = sum_j Ra(j,i) h_j and
+// ch = h . S_d with h = g / mu (sum_i w_i I_i = sum_i h_i psi_i), so that the level's
+// downward mean intensity is (rh . I+ + ch) / 2 as its downward flux is rc . I+ + cs
+template <int NN>
+struct RecBF {  // ZT (column-major) | t | rc | cs | rh | ch
+  static constexpr int Z = RecB<NN>::Z;
+  static constexpr int Tv = RecB<NN>::Tv;
+  static constexpr int Rc = RecB<NN>::Rc;
+  static constexpr int Cs = RecB<NN>::Cs;
+  static constexpr int Rh = Cs + 2;
+  static constexpr int Ch = Rh + even_up(NN);
+  static constexpr int pairs = (Ch + 2) / 2;
+};
 // Record traffic (layer records, back-substitution records) of a large chunk is written
 // once and read once, a whole kernel later, far beyond what the caches hold: there the
 // kernels use nontemporal loads and stores (the `nt` bit, NT = true) so that it does not
@@ -229,6 +243,30 @@ struct SweepArgs {
   int lean8;
 };
 
+// hd_solve_flx (the full flux record per level, hdisort.h HD_FLX_*): what its sweep and
+// back-substitution instantiations take beside SweepArgs (whose flux is then null)
+constexpr int kNFlx = 8;
+enum { kFlxRfldir = 0, kFlxRfldn, kFlxFlup, kFlxDfdt, kFlxUavg, kFlxUavgdn, kFlxUavgup,
+       kFlxUavgso };
+struct FlxArgs {
+  double* flx;        // [nwave*ncol][nlyr+1][kNFlx], level 0 = surface
+  const double* lvl;  // [3][nlyr+1][nsc] by solver level (0 = top), from hd_flx_level_kernel:
+                      // rfldir | uavgso | (1 - ssa_in) 4 pi of the layer above the level
+};
+// prologue of an hd_solve_flx chunk: the per-level terms that need the input optics
+struct FlxLevelArgs {
+  const double* prop;
+  const double* fbeam;
+  const double* umu0;
+  double* out;  // FlxArgs::lvl
+  long s0;
+  int nsc;
+  int nlyr;
+  int nprop;
+  int use_f;   // delta-M active (moments >= nstr available)
+  int f_slot;  // prop slot of chi_nstr = 1 + nstr
+};
+
 // chunk epilogue of the fused band sum: bflux[c] (=|+=) sum of the chunk's
 // partials of column c, in wave order (cmaj: register-path partials; else the
 // chunk flux buffer of the team path in wave-point order)
@@ -286,6 +324,14 @@ hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
 // register path, nstr 16: layer setup + adding sweep + back-substitution of one chunk in
 // one kernel (hd_column_kernel; la.scr unused -- no layer records)
 hipError_t launch_column_nn(int nn, const LayerArgs& la, const SweepArgs& sa, hipStream_t stream);
+// hd_solve_flx: the per-level prologue, the plain one-lane sweep and the back-substitution
+// with the second functional (register path), the one-wave team sweep with it (team path)
+hipError_t launch_flx_level(const FlxLevelArgs& fa, hipStream_t stream);
+hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream);
+hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
+                                 hipStream_t stream, bool tail);
+hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
+                                    hipStream_t stream);
 hipError_t launch_solve_chunk_team(int nn, const PlanckArgs* pa, const TaucArgs* ta,
                                    const LayerArgs& la, const SweepArgs& sa, hipStream_t stream,
                                    hipEvent_t* ev);
@@ -324,5 +370,6 @@ int set_global_error(int code, const char* fmt, ...);
 // doubles per (layer, solve) of the layer-operator and back-substitution records
 size_t layer_record_doubles(int nn);
 size_t bsub_record_doubles(int nn);
+size_t bsub_flx_record_doubles(int nn);  // hd_solve_flx's records (RecBF / the widened team record)
 
 }  // namespace hd

@@ -574,7 +574,6 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
   }
 }
 
-#if HD_AB_VARIANTS  // the one-wave team sweep: A/B build only (the product runs the lean one)
 // ============================================================================
 // K2 (team, MFMA): adding sweep + back-substitution, four solves per wave.
 // The register/team sweep's update per layer
@@ -588,10 +587,16 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
 // the back-substitution pass is hd_team_sweep_kernel's.  One wave per SIMD: at
 // two (256 registers) it spills 144 VGPRs and ran C5 at 0.81M solves/s against
 // 1.02M here and 0.97M for the VALU sweep (scripts/ab/sw_ab.sh).
+// As hd_solve's sweep it is in the A/B build only (the product runs the lean one).
+// FLX (hd_solve_flx, always built): the back-substitution record is widened by the
+// mean-intensity row rh_i = sum_j A(i,j) h_j and the scalar ch = h . Sd, h = g / mu,
+// after cs (stride ne2tf), and the upward pass emits the eight components of every
+// level to F->flx instead of the two fluxes.
 // ============================================================================
-template <int NN>
-__global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) {
-  __shared__ double lds[2 * kSet];
+template <int NN, bool FLX>
+__device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const FlxArgs* F,
+                                                     double* lds) {
+  constexpr int ne2 = FLX ? ne2tf<NN>() : ne2t<NN>();
   double* S0 = lds;
   double* S1 = lds + kSet;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
@@ -611,6 +616,7 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
   int st = 0;
   const double msk = act ? 1.0 : 0.0;
   const double g_i = Qc.g[ii] * msk;
+  const double h_i = g_i * Qc.rmu[ii];
 
   for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;
   lds_fence();
@@ -647,7 +653,7 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
 
   for (int lc = 0; lc < L; ++lc) {
     const double* rec = A.scr + ((size_t)lc * nsc + sl) * ne1t<NN>();
-    double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2t<NN>();
+    double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2;
     double* bw = (act && valid) ? bp : A.sink;
     // R~, T~ of the four problems in M layout (zero padding beyond NN)
     double rm[4][4], tm[4][4];
@@ -682,6 +688,15 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
       bw[NN * NN + NN + ii] = twopi * tq;
       const double cs = team_sum(g_i * sd);
       if (i == 0 && valid) bp[NN * NN + 2 * NN] = fma(twopi, cs, f0mu0 * eb);
+      if constexpr (FLX) {
+        double th = 0.0;
+        sfor<0, NN>([&](auto J) {
+          th = fma(ra[HD_K(J)], Qc.g[HD_K(J)] * Qc.rmu[HD_K(J)], th);
+        });
+        bw[NN * NN + 2 * NN + 1 + ii] = th;
+        const double ch = team_sum(h_i * sd);
+        if (i == 0 && valid) bp[NN * NN + 3 * NN + 1] = ch;
+      }
     }
     // W1 = I - R A on the matrix core, to team rows through LDS
     {
@@ -777,7 +792,7 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
       mprod<false>(li, x1, zm, h, c);  // ZT = U^-1 (L^-1 T)
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt) {
-        double* zr = A.bsub + ((size_t)lc * nsc + slm[tt]) * ne2t<NN>();
+        double* zr = A.bsub + ((size_t)lc * nsc + slm[tt]) * ne2;
         const bool ok = grp * 4 + tt < A.nsc;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -810,12 +825,39 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
   if (beam) esurf += alb * dirsurf / kPi;
   const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
   double ip = g_i * x;
-  double* fo = A.flux + (size_t)(A.flux_local ? (long)sl : s) * (L + 1) * 2;
+  double* fo = FLX ? nullptr : A.flux + (size_t)(A.flux_local ? (long)sl : s) * (L + 1) * 2;
   double chk = 0.0;
+  // FLX: the level's eight components (team lane 0 stores them)
+  auto emit8 = [&](int lc, double up, double dn, double hu, double hdn) {
+    const size_t nl = (size_t)(L + 1) * nsc;
+    const int lev = L - lc;
+    const double rfldir = F->lvl[(size_t)lc * nsc + sl];
+    const double uavgso = F->lvl[nl + (size_t)lc * nsc + sl];
+    const double absl = F->lvl[2 * nl + (size_t)lc * nsc + sl];
+    const double bl = A.planck ? A.planckv[(size_t)lev * nsc + sl] : 0.0;
+    const double uavgup = 0.5 * hu, uavgdn = 0.5 * hdn;
+    const double uavg = uavgup + uavgdn + uavgso;
+    if (i == 0 && valid) {
+      double* o = F->flx + ((size_t)s * (L + 1) + lev) * kNFlx;
+      o[kFlxRfldir] = rfldir;
+      o[kFlxRfldn] = dn - rfldir;
+      o[kFlxFlup] = up;
+      o[kFlxDfdt] = absl * (uavg - bl);
+      o[kFlxUavg] = uavg;
+      o[kFlxUavgdn] = uavgdn;
+      o[kFlxUavgup] = uavgup;
+      o[kFlxUavgso] = uavgso;
+    }
+  };
   {
     const double up = team_sum(g_i * ip);
     const double dn = team_sum(g_i * fma(rgrow, x, sd));
-    if (i == 0 && valid) {
+    if constexpr (FLX) {
+      const double hu = team_sum(h_i * ip);
+      const double hdn = team_sum(h_i * fma(rgrow, x, sd));
+      emit8(L, twopi * up, twopi * dn + dirsurf, hu, hdn);
+      chk += hu + hdn;
+    } else if (i == 0 && valid) {
       fo[0] = twopi * up;
       fo[1] = twopi * dn + dirsurf;
     }
@@ -823,7 +865,7 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
   }
   // ---- back-substitution bottom -> top ----
   for (int lc = L - 1; lc >= 0; --lc) {
-    const double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2t<NN>();
+    const double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2;
     double nip = bp[NN * NN + ii] * msk;
     sfor<0, NN>([&](auto J) {
       const double z = bp[ii * NN + HD_K(J)] * msk;
@@ -833,7 +875,13 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
     const double up = team_sum(g_i * nip);
     const double dn = team_sum(rc * nip);
     ip = nip;
-    if (i == 0 && valid) {
+    if constexpr (FLX) {
+      const double rh = bp[NN * NN + 2 * NN + 1 + ii] * msk;
+      const double hu = team_sum(h_i * nip);
+      const double hdn = bp[NN * NN + 3 * NN + 1] + team_sum(rh * nip);
+      emit8(lc, twopi * up, bp[NN * NN + 2 * NN] + dn, hu, hdn);
+      chk += hu + hdn;
+    } else if (i == 0 && valid) {
       const int lev = L - lc;
       fo[2 * lev] = twopi * up;
       fo[2 * lev + 1] = bp[NN * NN + 2 * NN] + dn;
@@ -846,7 +894,21 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) 
     if (st & 0x0F) atomicOr(A.anyerr, 1);
   }
 }
+
+#if HD_AB_VARIANTS  // hd_solve's one-wave team sweep: A/B build only
+template <int NN>
+__global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) {
+  __shared__ double lds[2 * kSet];
+  team_mfma_sweep_body<NN, false>(A, nullptr, lds);
+}
 #endif  // HD_AB_VARIANTS
+// hd_solve_flx's team sweep
+template <int NN>
+__global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
+  __shared__ double lds[2 * kSet];
+  team_mfma_sweep_body<NN, true>(A, &F, lds);
+}
+
 
 // ============================================================================
 // K2 (team, MFMA), lean: the same sweep and back-substitution as
@@ -1869,6 +1931,29 @@ hipError_t launch_team_sweep_mfma(int nn, const SweepArgs& sa, hipStream_t strea
     case 14: return launch_sweep<14>(sa, stream);
     case 15: return launch_sweep<15>(sa, stream);
     case 16: return launch_sweep<16>(sa, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <int NN>
+static hipError_t launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
+  static_assert(ne2tf<NN>() % 2 == 0, "16-byte aligned records");
+  hipLaunchKernelGGL(hd_team_mfma_sweep_flx_kernel<NN>, dim3((unsigned)((sa.nsc + 3) / 4)),
+                     dim3(64), 0, stream, sa, fx);
+  return hipGetLastError();
+}
+
+hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
+                                    hipStream_t stream) {
+  switch (nn) {
+    case 9: return launch_sweep_flx<9>(sa, fx, stream);
+    case 10: return launch_sweep_flx<10>(sa, fx, stream);
+    case 11: return launch_sweep_flx<11>(sa, fx, stream);
+    case 12: return launch_sweep_flx<12>(sa, fx, stream);
+    case 13: return launch_sweep_flx<13>(sa, fx, stream);
+    case 14: return launch_sweep_flx<14>(sa, fx, stream);
+    case 15: return launch_sweep_flx<15>(sa, fx, stream);
+    case 16: return launch_sweep_flx<16>(sa, fx, stream);
     default: return hipErrorInvalidValue;
   }
 }

@@ -348,5 +348,10 @@ template <int NN>
 constexpr int ne2t() {
   return (NN * NN + 2 * NN + 2) & ~1;
 }
+// hd_solve_flx's team record: ne2t's elements, then rh (NN) and ch after cs
+template <int NN>
+constexpr int ne2tf() {
+  return (NN * NN + 3 * NN + 3) & ~1;
+}
 
 }  // namespace hd

@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from .index import IEX, ISS, IPM  # noqa: F401  (re-exported like disort::index)
+from .index import NFLX
 from .rtsolver import RTSolver
 
 # cdisort's disort_flag fields as pydisort's flag string names them (the Disort-flags
@@ -305,7 +306,29 @@ class Disort(RTSolver):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
             raise
 
-    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None):
+    def forward_flx(self, prop: torch.Tensor, bc: Optional[Dict[str, torch.Tensor]] = None,
+                    temf: Optional[torch.Tensor] = None, *,
+                    status: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """DISORT's full flux record at every level, (nwave, ncol, nlyr+1, NFLX) in the
+        component order of cdisort's disort_radiant (index.IRFLDIR .. IUAVGSO): direct
+        beam, diffuse down, up, flux divergence dF/dtau, mean intensity and its down /
+        up / direct-beam parts (hd_solve_flx; definitions in include/hdisort.h).  Level
+        0 is the surface.  On the input's device: CPU tensors are staged with torch
+        copies and the record comes back on the CPU."""
+        if self.usrtau:
+            raise RuntimeError("Disort.forward_flx: the flux record is at the layer boundaries "
+                               "(clear the 'usrtau' flag)")
+        if not self.onlyfl:
+            raise RuntimeError("Disort.forward_flx: a flux-only path (set the 'onlyfl' flag)")
+        try:
+            return self._forward(prop, bc, temf, status=status, out=out, flx=True)
+        except RuntimeError as err:
+            if "at least one solve failed" in str(err) and _beam_hint(bc):
+                raise RuntimeError(str(err) + _beam_hint(bc)) from err
+            raise
+
+    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None, flx=False):
         op = self.options
         ds = op.ds()
         bc = {} if bc is None else bc
@@ -331,7 +354,8 @@ class Disort(RTSolver):
         in_dev = prop.device
         dev = in_dev if in_dev.type == "cuda" else torch.device("cuda", int(op.device()))
         f64 = torch.float64
-        if in_dev.type != "cuda" and not self.radiance and out is None and status is None:
+        if (in_dev.type != "cuda" and not self.radiance and out is None and status is None
+                and not flx):
             # pydisort's CPU-tensor contract: the library's host-array entry points
             # (hd_solve_host / hd_solve_band_host) copy the arrays over in pieces
             # beside the solve of the previous piece
@@ -370,14 +394,16 @@ class Disort(RTSolver):
             wl, wu = self._waves[1], self._waves[2]
             keep += [tf, wl, wu]
         nlev = ds.ntau if self.radiance else nlyr + 1
+        ncomp = NFLX if flx else 2
         if out is None:
             flux = None if band is not None else \
-                torch.empty((nwave, ncol, nlev, 2), dtype=f64, device=dev)
+                torch.empty((nwave, ncol, nlev, ncomp), dtype=f64, device=dev)
         else:
             if (out.device != dev or out.dtype != f64 or not out.is_contiguous()
-                    or tuple(out.shape) != (nwave, ncol, nlev, 2)):
-                raise RuntimeError("Disort.forward: out must be a contiguous float64 tensor "
-                                   f"of shape {(nwave, ncol, nlev, 2)} on {dev}")
+                    or tuple(out.shape) != (nwave, ncol, nlev, ncomp)):
+                who = "Disort.forward_flx" if flx else "Disort.forward"
+                raise RuntimeError(f"{who}: out must be a contiguous float64 tensor "
+                                   f"of shape {(nwave, ncol, nlev, ncomp)} on {dev}")
             flux = out
         if status is not None and (status.device != dev or status.dtype != torch.int32
                                    or not status.is_contiguous()
@@ -418,7 +444,12 @@ class Disort(RTSolver):
                                                stream.cuda_stream)
             del keep
             return bout.to(in_dev) if in_dev.type != "cuda" else bout
-        if self.radiance:
+        if flx:
+            with torch.cuda.device(dev):
+                _context(dev.index).solve_flx(cfg, inp, flux.data_ptr(),
+                                              status.data_ptr() if status is not None else None,
+                                              stream.cuda_stream)
+        elif self.radiance:
             self._forward_radiance(cfg, inp, flux, status, stream, bc, dev, keep, nwave, ncol)
         else:
             with torch.cuda.device(dev):

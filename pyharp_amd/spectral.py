@@ -57,6 +57,29 @@ def band_flux(flux: torch.Tensor, weights: torch.Tensor,
     return out
 
 
+def band_flx(flx: torch.Tensor, weights: torch.Tensor,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum_g w_g flx_g for the full flux record (G, ncol, nlev, NFLX) of
+    Disort.forward_flx and weights (G,), in g order: (ncol, nlev, NFLX).  The same
+    kernel as band_flux (hd_band_flux sums (level, component) pairs without looking
+    at them: nlev * NFLX / 2 "levels" of two)."""
+    from .index import NFLX
+    f = _dev_f64(flx, "band_flx")
+    if f.dim() != 4 or f.shape[3] != NFLX:
+        raise RuntimeError(f"band_flx: flx must be (G, ncol, nlev, {NFLX})")
+    G, ncol, nlev, _ = f.shape
+    w = torch.as_tensor(weights, dtype=torch.float64).to(f.device).contiguous()
+    if w.numel() != G:
+        raise RuntimeError(f"band_flx: {w.numel()} weights for {G} g-points")
+    if out is None:
+        out = torch.empty((ncol, nlev, NFLX), dtype=torch.float64, device=f.device)
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.load().hd_band_flux(f.data_ptr(), w.data_ptr(), G, ncol,
+                                            nlev * (NFLX // 2), out.data_ptr(),
+                                            _stream(f.device)))
+    return out
+
+
 def heating_rate(bflux: torch.Tensor, dz: torch.Tensor, rho: torch.Tensor,
                  cp: float) -> torch.Tensor:
     """dT/dt (ncol, nlyr) [K/s] = -(1/(rho c_p)) d(F_up - F_dn)/dz from the band

@@ -13,7 +13,8 @@ SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "pyha
                    "hd_team_mfma.hip")
 s = open(SRC).read()
 i0 = s.index("__global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) {")
-i1 = s.index("#if HD_AB_VARIANTS  // the one-wave team sweep")
+i1 = s.index("// K2 (team, MFMA): adding sweep + back-substitution, four solves per wave.")
+i1 = s.rindex("// ====", 0, i1)  # the banner line above it: the end of the layer kernel
 head, body, tail = s[:i0], s[i0:i1], s[i1:]
 
 
