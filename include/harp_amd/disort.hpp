@@ -32,12 +32,14 @@
 #include <torch/nn/modules/container/any.h>
 #include <torch/torch.h>
 
+#include <cctype>
 #include <cmath>
 #include <map>
 #include <memory>
 #include <set>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../hdisort.h"
@@ -156,6 +158,48 @@ inline std::set<std::string> parse_flags(const std::string& s) {
     if (!tok.empty()) out.insert(tok);
   }
   return out;
+}
+
+// harp's `outdirs` string, "(zenith,azimuth) (zenith,azimuth) ..." with both angles in
+// degrees (src/radiation/radiation.hpp:31, radiation_band.hpp:30), as the umu / phi
+// arguments of DisortImpl::forward_rays: float64 (nray) tensors, mu = cos(zenith) and
+// the azimuth in DEGREES.  harp's own parser returns one float32 (nray, 2) tensor with
+// the azimuth in radians; cdisort and libhdisort take degrees.
+inline std::pair<torch::Tensor, torch::Tensor> parse_radiation_directions(const std::string& s) {
+  std::vector<double> mu, phi;
+  size_t i = 0;
+  auto skip = [&] { while (i < s.size() && std::isspace((unsigned char)s[i])) ++i; };
+  auto number = [&](double& v) {
+    skip();
+    size_t used = 0;
+    try {
+      v = std::stod(s.substr(i), &used);
+    } catch (std::exception const&) {
+      used = 0;
+    }
+    TORCH_CHECK(used > 0 && std::isfinite(v), "parse_radiation_directions: expected a number at "
+                "position ", i, " of '", s, "'");
+    i += used;
+    skip();
+  };
+  for (skip(); i < s.size(); skip()) {
+    double zen = 0.0, azi = 0.0;
+    TORCH_CHECK(s[i] == '(', "parse_radiation_directions: expected '(' at position ", i,
+                " of '", s, "'");
+    ++i;
+    number(zen);
+    TORCH_CHECK(i < s.size() && s[i] == ',', "parse_radiation_directions: expected ',' at "
+                "position ", i, " of '", s, "'");
+    ++i;
+    number(azi);
+    TORCH_CHECK(i < s.size() && s[i] == ')', "parse_radiation_directions: expected ')' at "
+                "position ", i, " of '", s, "'");
+    ++i;
+    mu.push_back(std::cos(zen * (3.14159265358979323846 / 180.0)));
+    phi.push_back(azi);
+  }
+  TORCH_CHECK(!mu.empty(), "parse_radiation_directions: no '(zenith,azimuth)' pair in '", s, "'");
+  return {torch::tensor(mu, torch::kFloat64), torch::tensor(phi, torch::kFloat64)};
 }
 
 class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
@@ -321,6 +365,29 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     return x.in_dev.is_cuda() ? bflux : bflux.to(x.in_dev);
   }
 
+  //! radiances (nwave, ncol, ntau, nray) along paired outgoing directions
+  //! (hd_solve_rays): umu / phi float64 (nray) -- shared -- or (ncol, nray) -- each
+  //! column's own; umu the polar cosine (> 0 upward), phi in DEGREES (harp's outdirs
+  //! list, parse_radiation_directions below).  Exact at every ray: this replaces the
+  //! grid solve + bilinear interpolation of the legacy CalBandRadiance
+  //! (rt_solver_disort.cpp_:210-286).  Needs a module without onlyfl; depths are
+  //! user_tau with usrtau, else the layer boundaries; user_mu / user_phi are not used.
+  torch::Tensor forward_rays(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
+                             torch::Tensor temf, torch::Tensor umu, torch::Tensor phi) {
+    return solve_rays("Disort.forward_rays", prop, bc, temf, umu, phi, torch::Tensor(), nullptr);
+  }
+
+  //! band radiance (ncol, ntau, nray) = sum_w weights[w] rad[w] with the sum fused into
+  //! the solve (the legacy btoa(n) += wght[b] * toa(b, n)); one fma per wave in wave
+  //! order, no atomics.  Per-wave radiances are stored only if rad is given (it is
+  //! set to a (nwave, ncol, ntau, nray) tensor on the input's device).
+  torch::Tensor forward_rays_band(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
+                                  torch::Tensor temf, torch::Tensor umu, torch::Tensor phi,
+                                  torch::Tensor weights, torch::Tensor* rad = nullptr) {
+    TORCH_CHECK(weights.defined(), "Disort.forward_rays_band: weights are required");
+    return solve_rays("Disort.forward_rays_band", prop, bc, temf, umu, phi, weights, rad);
+  }
+
  protected:
   FORWARD_HAS_DEFAULT_ARGS({2, torch::nn::AnyValue(torch::Tensor())})
 
@@ -346,6 +413,46 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
       return it == b.end() ? nullptr : it->second.data_ptr<double>();
     }
   };
+
+  // forward_rays (weights undefined) and forward_rays_band
+  torch::Tensor solve_rays(const char* who, torch::Tensor prop,
+                           std::map<std::string, torch::Tensor>* bc, torch::Tensor temf,
+                           torch::Tensor umu, torch::Tensor phi, torch::Tensor weights,
+                           torch::Tensor* rad_out) {
+    TORCH_CHECK(!onlyfl_, who, ": radiances are off (clear the 'onlyfl' flag)");
+    TORCH_CHECK(prop.dim() == 4, who, ": prop must be (nwave, ncol, nlyr, nprop)");
+    TORCH_CHECK(umu.defined() && phi.defined() && umu.scalar_type() == torch::kFloat64 &&
+                    phi.scalar_type() == torch::kFloat64,
+                who, ": umu and phi must be float64 tensors");
+    TORCH_CHECK((umu.dim() == 1 || (umu.dim() == 2 && umu.size(0) == prop.size(1))) &&
+                    umu.size(-1) >= 1,
+                who, ": umu must be (nray) or (ncol, nray)");
+    TORCH_CHECK(phi.sizes() == umu.sizes(), who, ": phi must have umu's shape");
+    const bool band = weights.defined();
+    Batch x = prepare(prop, bc, temf, /*stage=*/true);
+    auto const& d = options.ds();
+    const int nray = (int)umu.size(-1);
+    auto mu = umu.to(x.f64).contiguous(), ph = phi.to(x.f64).contiguous();
+    torch::Tensor w, brad, rad;
+    if (band) {
+      w = weights.to(x.f64).reshape({-1}).contiguous();
+      TORCH_CHECK(w.size(0) == x.nwave, who, ": ", w.size(0), " weights for ", x.nwave, " waves");
+      brad = torch::empty({x.ncol, d.ntau, nray}, x.f64);
+    }
+    if (!band || rad_out) rad = torch::empty({x.nwave, x.ncol, d.ntau, nray}, x.f64);
+    hd_rays rays{nray, umu.dim() == 2 ? 1 : 0, mu.data_ptr<double>(), ph.data_ptr<double>(),
+                 usrtau_ ? d.ntau : 0, d.utau.data(), x.bp("phi0"), corint_ ? 1 : 0,
+                 band ? w.data_ptr<double>() : nullptr,
+                 band ? brad.data_ptr<double>() : nullptr};
+    auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
+    const int rc = hd_solve_rays(context(x.dev.index()), &x.cfg, &x.in, &rays, nullptr,
+                                 rad.defined() ? rad.data_ptr<double>() : nullptr, nullptr,
+                                 reinterpret_cast<void*>(stream));
+    TORCH_CHECK(rc == HD_OK, "DisortWrapper::Run failed: ", hd_last_error(context(x.dev.index())));
+    if (rad_out) *rad_out = x.in_dev.is_cuda() ? rad : rad.to(x.in_dev);
+    auto res = band ? brad : rad;
+    return x.in_dev.is_cuda() ? res : res.to(x.in_dev);
+  }
 
   // stage: CPU tensors go to the device (entry points without a host-array twin)
   Batch prepare(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,

@@ -120,6 +120,13 @@ int hd_rfm_attenuate(const hd_rfm_table *t, const double *conc, int ncol, int nl
 int hd_band_flux(const double *flux, const double *weight, int nwave, int ncol, int nlev,
                  double *bflux, void *stream);
 
+/* out [n] = sum_w weight[w] x[w][n] for any per-wave field (the band radiances of
+ * hdisort.h's ray call: n = ncol*ntau*nray): out = 0, then out = fma(weight[w], x[w], out)
+ * for w = 0, 1, ... -- the same sequence for every element and every nwave, so it is
+ * bitwise equal to the sum that call fuses into the solve.  All DEVICE pointers. */
+int hd_band_sum(const double *x, const double *weight, int nwave, long n, double *out,
+                void *stream);
+
 /* dTdt [ncol][nlyr] K/s from bflux [ncol][nlyr+1][2], dz and rho [ncol][nlyr] */
 int hd_heating_rate(const double *bflux, const double *dz, const double *rho, double cp,
                     int ncol, int nlyr, double *dTdt, void *stream);

@@ -287,6 +287,61 @@ int hd_solve_radiance(hd_context *ctx, const hd_config *cfg, const hd_inputs *in
                       const hd_radiance *rad, double *flux, double *uu, int *status,
                       void *stream);
 
+/*
+ * Ray radiances: the intensity path along nray paired outgoing directions
+ * (umu_r, phi_r) instead of a umu x phi grid -- harp's `outdirs` list
+ * (src/radiation/radiation.hpp:31, radiation_band.hpp:30), which the legacy driver
+ * served by solving on the grid the directions span and interpolating uu bilinearly
+ * onto each ray (src/rtsolver/rt_solver_disort.cpp_:210-286).  Here every ray is
+ * evaluated exactly by the source-function integration at its own cosine and azimuth:
+ *   rad[w][c][lu][r] = sum_m I_m(utau_lu, umu_r) cos(m (phi_r - phi0))
+ * plus, with corint = 1, the Nakajima-Tanaka TMS + IMS term at that one direction;
+ * I_m are the per-mode radiances of the grid call, so with per_column = 0 the result
+ * agrees with the diagonal uu[w][c][j=r][lu][iu=r] of a grid call with umu = umu_r,
+ * phi = phi_r.  n rays cost n user-angle integrations, n azimuth sums and n stored
+ * values per depth (an n x n grid: n, n^2, n^2).  The directions may differ from
+ * column to column (per_column = 1: a pixel's own emission angle and azimuth).
+ *
+ * Band sum: with brad (and weight) the weighted sum over the wave axis that harp's
+ * callers apply next (btoa(n) += wght[b] * toa(b, n)) is formed in the ray epilogue,
+ *   brad[c][lu][r] = sum_w weight[w] rad[w][c][lu][r],
+ * one fma per wave in ascending w, the same sequence for every element, no atomics:
+ * independent of the chunk size and of chunks that start inside a wave, and bitwise
+ * equal to hd_band_sum (hdharp.h) of a stored rad.  rad may then be NULL: per-wave
+ * radiances are not stored.
+ *
+ * A ray whose umu is not finite, is 0 or exceeds 1 in magnitude can only be seen on
+ * the device: every solve of its column (every solve when the rays are shared) sets
+ * HD_STATUS_BAD_INPUT (a synchronous call returns HD_ENUMERIC) and that ray's
+ * radiances are NaN; the column's other rays and the other columns are unaffected.
+ * The user-angle kernels never see such a value (they run on 1 in its place).
+ *
+ * Host-side validation (nstr, ntau/utau, corint) as for the grid call; rad and brad
+ * both NULL, or brad without weight, is HD_EINVAL.  Not capturable into a HIP graph
+ * (HD_EINVAL under capture): utau is a host array.  status / stream / return codes
+ * as for the grid call.  At nstr 18..32 shared rays run the team user-angle kernels;
+ * per-column rays run the one-lane user-angle kernel.
+ * Outputs (device):
+ *   rad  [nwave][ncol][ntau][nray]  depths in the user's order, as in uu; or NULL
+ *        when brad is given
+ *   flux [nwave][ncol][ntau][2]  as for the grid call, or NULL (not computed)
+ */
+typedef struct hd_rays {
+  int nray;             /* rays per column, >= 1                                        */
+  int per_column;       /* 0: umu/phi are [nray], shared; 1: [ncol][nray]               */
+  const double *umu;    /* DEVICE polar cosines, nonzero, > 0 upward, |umu| <= 1        */
+  const double *phi;    /* DEVICE azimuths [deg]                                        */
+  int ntau;             /* as hd_radiance: HOST utau[ntau] (unscaled, >= 0, ascending); */
+  const double *utau;   /*   ntau = 0: the nlyr+1 layer boundaries of every column      */
+  const double *phi0;   /* DEVICE [nwave*ncol] beam azimuth [deg] or NULL (0)           */
+  int corint;           /* 0 / 1 exactly as hd_radiance                                 */
+  const double *weight; /* DEVICE [nwave] or NULL                                       */
+  double *brad;         /* DEVICE [ncol][ntau][nray], overwritten; needs weight         */
+} hd_rays;
+
+int hd_solve_rays(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                  const hd_rays *rays, double *flux, double *rad, int *status, void *stream);
+
 /* host helper: the double-Gauss quadrature the kernels use (nstr/2 nodes on (0,1)) */
 int hd_quadrature(int nstr, double *mu, double *w);
 

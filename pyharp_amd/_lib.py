@@ -27,11 +27,13 @@ EXPORTED = ("hd_version", "hd_last_error", "hd_context_create", "hd_context_dest
             "hd_context_set_chunk", "hd_context_set_timing", "hd_context_set_max_sweeps",
             "hd_context_get_timing",
             "hd_context_reserve", "hd_solve", "hd_solve_flx", "hd_solve_band", "hd_solve_host",
-            "hd_solve_band_host", "hd_solve_radiance", "hd_quadrature", "hd_chunk_solves")
+            "hd_solve_band_host", "hd_solve_radiance", "hd_solve_rays", "hd_quadrature",
+            "hd_chunk_solves")
 
 # every symbol include/hdharp.h declares (harp-side steps around the solve)
 HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rfm_attenuate",
-                 "hd_band_flux", "hd_heating_rate", "hd_spherical_flux_correction")
+                 "hd_band_flux", "hd_band_sum", "hd_heating_rate",
+                 "hd_spherical_flux_correction")
 HD_COORD_WAVELENGTH, HD_COORD_WAVENUMBER = 0, 1
 
 # every symbol include/hdnc.h declares (netCDF readers, host code)
@@ -72,6 +74,12 @@ class HdRadiance(ctypes.Structure):
     _fields_ = [("ntau", ctypes.c_int), ("utau", _dp), ("numu", ctypes.c_int), ("umu", _dp),
                 ("nphi", ctypes.c_int), ("phi", _dp), ("phi0", _dp), ("onlyfl", ctypes.c_int),
                 ("corint", ctypes.c_int)]
+
+
+class HdRays(ctypes.Structure):
+    _fields_ = [("nray", ctypes.c_int), ("per_column", ctypes.c_int), ("umu", _dp), ("phi", _dp),
+                ("ntau", ctypes.c_int), ("utau", _dp), ("phi0", _dp), ("corint", ctypes.c_int),
+                ("weight", _dp), ("brad", _dp)]
 
 
 class HdBand(ctypes.Structure):
@@ -126,6 +134,10 @@ def load(path: str = LIB_PATH):
                                       ctypes.POINTER(HdInputs), ctypes.POINTER(HdRadiance),
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p]
+    lib.hd_solve_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                  ctypes.POINTER(HdInputs), ctypes.POINTER(HdRays),
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p]
     lib.hd_quadrature.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double)]
     ci, cd = ctypes.c_int, ctypes.c_double
@@ -138,6 +150,7 @@ def load(path: str = LIB_PATH):
     lib.hd_rfm_attenuate.argtypes = [ctypes.POINTER(HdRfmTable), _dp, ci, ci, ci, _dp, _dp, _dp,
                                      _dp]
     lib.hd_band_flux.argtypes = [_dp, _dp, ci, ci, ci, _dp, _dp]
+    lib.hd_band_sum.argtypes = [_dp, _dp, ci, ctypes.c_long, _dp, _dp]
     lib.hd_heating_rate.argtypes = [_dp, _dp, _dp, cd, ci, ci, _dp, _dp]
     lib.hd_spherical_flux_correction.argtypes = [_dp, _dp, _dp, _dp, ci, ci, _dp]
     lib.hd_nc_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p),
@@ -247,6 +260,17 @@ class Context:
                                       ctypes.c_void_p(uu_ptr or 0),
                                       ctypes.c_void_p(status_ptr or 0),
                                       ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+
+    def solve_rays(self, cfg: HdConfig, inp: HdInputs, rays: HdRays, flux_ptr: int | None,
+                   rad_ptr: int | None, status_ptr: int | None, stream_ptr: int | None):
+        """hd_solve_rays: radiances along paired directions; rad and/or rays.brad."""
+        rc = load().hd_solve_rays(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                  ctypes.byref(rays), ctypes.c_void_p(flux_ptr or 0),
+                                  ctypes.c_void_p(rad_ptr or 0),
+                                  ctypes.c_void_p(status_ptr or 0),
+                                  ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
 

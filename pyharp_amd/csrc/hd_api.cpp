@@ -1292,13 +1292,14 @@ int hd_solve_band_host(hd_context* ctx, const hd_config* cfg, const hd_inputs* i
 namespace {
 
 int validate_rad(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
-                 const hd_radiance* rad, double* flux, double* uu) {
-  int rc = validate(ctx, cfg, in, flux);
+                 const hd_radiance* rad, double* flux, double* uu, bool rays = false) {
+  const char* who = rays ? "hd_solve_rays" : "hd_solve_radiance";
+  int rc = validate(ctx, cfg, in, flux, who);
   if (rc) return rc;
-  if (!rad) return fail(ctx, HD_EINVAL, "hd_solve_radiance: null radiance config");
+  if (!rad) return fail(ctx, HD_EINVAL, "%s: null radiance config", who);
   const int nn = cfg->nstr / 2;
   if (nn > hd::kRadMaxNN)
-    return fail(ctx, HD_EINVAL, "hd_solve_radiance: nstr=%d; the intensity path supports nstr <= %d",
+    return fail(ctx, HD_EINVAL, "%s: nstr=%d; the intensity path supports nstr <= %d", who,
                 cfg->nstr, 2 * hd::kRadMaxNN);
   const bool radiances = rad->onlyfl == 0;
   const int nlyr = cfg->nlyr;
@@ -1307,15 +1308,15 @@ int validate_rad(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   const int nphi = radiances ? rad->nphi : 0;
   if (rad->corint != 0 && rad->corint != 1)
     return fail(ctx, HD_EINVAL,
-                "hd_solve_radiance: corint=%d; 0 (none) and 1 (Nakajima-Tanaka, cdisort's "
+                "%s: corint=%d; 0 (none) and 1 (Nakajima-Tanaka, cdisort's "
                 "old_intensity_correction) are implemented, cdisort's new correction is not",
-                rad->corint);
+                who, rad->corint);
   if (rad->ntau < 0 || (rad->ntau > 0 && !rad->utau))
-    return fail(ctx, HD_EINVAL, "hd_solve_radiance: ntau=%d needs utau", rad->ntau);
+    return fail(ctx, HD_EINVAL, "%s: ntau=%d needs utau", who, rad->ntau);
   for (int i = 0; i < rad->ntau; ++i)
     if (!(rad->utau[i] >= 0.0) || (i > 0 && !(rad->utau[i] >= rad->utau[i - 1])))
-      return fail(ctx, HD_EINVAL, "hd_solve_radiance: utau must be >= 0 and ascending");
-  if (radiances) {
+      return fail(ctx, HD_EINVAL, "%s: utau must be >= 0 and ascending", who);
+  if (radiances && !rays) {
     if (numu < 1 || !rad->umu || nphi < 1 || !rad->phi || !uu)
       return fail(ctx, HD_EINVAL,
                   "hd_solve_radiance: radiances need numu >= 1, nphi >= 1, umu, phi and uu");
@@ -1327,9 +1328,13 @@ int validate_rad(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   return HD_OK;
 }
 
+// rays = null: the grid call (rad->umu x rad->phi, host arrays, into uu).  rays given
+// (hd_solve_rays): rad is its view of them (numu = nray, nphi = 1, umu / phi unused),
+// uu is the per-wave ray output or null
 int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
-                const hd_radiance* rad, double* flux, double* uu, int*& status,
-                hipStream_t stream) {
+                const hd_radiance* rad, const hd_rays* rays, double* flux, double* uu,
+                int*& status, hipStream_t stream) {
+  const char* who = rays ? "hd_solve_rays" : "hd_solve_radiance";
   int rc = HD_OK;
   const int nn = cfg->nstr / 2;
   const bool radiances = rad->onlyfl == 0;
@@ -1349,11 +1354,13 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   // freed, and nothing may be allocated under capture)
   if (ctx->capturing)
     return fail(ctx, HD_EINVAL,
-                "hd_solve_radiance: not capturable into a HIP graph (host user grid)");
+                "%s: not capturable into a HIP graph (host user grid)", who);
   rc = ensure_rad_tables(ctx);
   if (rc) return rc;
-  // user grid on the device: umu | phi | utau
-  const size_t ngrid = (size_t)numu + nphi + rad->ntau;
+  // user grid on the device: umu | phi | utau; rays: their cosines with the bad ones
+  // replaced (launch_ray_cosines) | utau, the azimuths read from the caller's array
+  const size_t ncos = rays ? (size_t)(rays->per_column ? in->ncol : 1) * numu : (size_t)numu;
+  const size_t ngrid = rays ? ncos + rad->ntau : (size_t)numu + nphi + rad->ntau;
   if (ngrid > ctx->rad_grid_len) {
     drain(ctx);
     if (ctx->rad_grid) (void)hipFree(ctx->rad_grid);
@@ -1364,9 +1371,13 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   }
   double* d_umu = ctx->rad_grid;
   double* d_phi = d_umu + numu;
-  double* d_utau = d_phi + nphi;
-  if (numu) HD_HIP(ctx, hipMemcpyAsync(d_umu, rad->umu, numu * sizeof(double), hipMemcpyHostToDevice, stream));
-  if (nphi) HD_HIP(ctx, hipMemcpyAsync(d_phi, rad->phi, nphi * sizeof(double), hipMemcpyHostToDevice, stream));
+  double* d_utau = rays ? d_umu + ncos : d_phi + nphi;
+  if (rays) {
+    HD_HIP(ctx, hd::launch_ray_cosines(rays->umu, d_umu, (long)ncos, stream));
+  } else {
+    if (numu) HD_HIP(ctx, hipMemcpyAsync(d_umu, rad->umu, numu * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (nphi) HD_HIP(ctx, hipMemcpyAsync(d_phi, rad->phi, nphi * sizeof(double), hipMemcpyHostToDevice, stream));
+  }
   if (rad->ntau)
     HD_HIP(ctx, hipMemcpyAsync(d_utau, rad->utau, rad->ntau * sizeof(double), hipMemcpyHostToDevice, stream));
 
@@ -1438,7 +1449,7 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
     a.tauc = beam ? r_tauc : nullptr;
     a.taus = r_taus;
     a.umu = d_umu;
-    a.phi = d_phi;
+    a.phi = rays ? rays->phi : d_phi;
     a.utau = rad->ntau > 0 ? d_utau : nullptr;
     a.rsw = r_sw;
     a.rrd = r_rd;
@@ -1447,7 +1458,14 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
     a.cst = r_cst;
     a.radm = r_radm;
     a.flux = flux;
-    a.uu = uu;
+    a.uu = rays ? nullptr : uu;
+    if (rays) {
+      a.umu_stride = rays->per_column ? numu : 0;
+      a.ray_umu = rays->umu;
+      a.weight = rays->weight;
+      a.rad = uu;
+      a.brad = rays->brad;
+    }
     a.status = status;
     a.anyerr = ctx->anyerr;
     a.s0 = s0;
@@ -1467,7 +1485,7 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
     a.sink = ctx->sink;
     hipError_t e = hd::launch_rad_chunk(nn, a, radiances, stream);
     if (e != hipSuccess)
-      return fail(ctx, HD_EHIP, "hd_solve_radiance: launch failed: %s", hipGetErrorString(e));
+      return fail(ctx, HD_EHIP, "%s: launch failed: %s", who, hipGetErrorString(e));
   }
   return HD_OK;
 }
@@ -1485,7 +1503,39 @@ int hd_solve_radiance(hd_context* ctx, const hd_config* cfg, const hd_inputs* in
   if (rc) return rc;
   if ((long)in->nwave * in->ncol == 0) return HD_OK;
   return run_solve(ctx, status, stream, "hd_solve_radiance", [&](int*& st, hipStream_t s) {
-    return rad_enqueue(ctx, cfg, in, rad, flux, uu, st, s);
+    return rad_enqueue(ctx, cfg, in, rad, nullptr, flux, uu, st, s);
+  });
+}
+
+int hd_solve_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                  const hd_rays* rays, double* flux, double* rad, int* status, void* stream) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_rays: null context");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!rays) return fail(ctx, HD_EINVAL, "hd_solve_rays: null ray config");
+  if (!rad && !rays->brad)
+    return fail(ctx, HD_EINVAL, "hd_solve_rays: rad and brad both NULL: nothing to compute");
+  if (rays->brad && !rays->weight)
+    return fail(ctx, HD_EINVAL, "hd_solve_rays: brad needs weight");
+  if (rays->nray < 1 || !rays->umu || !rays->phi)
+    return fail(ctx, HD_EINVAL, "hd_solve_rays: rays need nray >= 1, umu and phi");
+  if (rays->per_column != 0 && rays->per_column != 1)
+    return fail(ctx, HD_EINVAL, "hd_solve_rays: per_column=%d must be 0 or 1", rays->per_column);
+  // the rest as hd_solve_radiance (nstr, ntau/utau, corint); the cosines are device
+  // data, checked by the kernels.  flux is optional: validate against a stand-in
+  hd_radiance view{};
+  view.ntau = rays->ntau;
+  view.utau = rays->utau;
+  view.numu = rays->nray;
+  view.nphi = 1;
+  view.phi0 = rays->phi0;
+  view.onlyfl = 0;
+  view.corint = rays->corint;
+  double* out = rad ? rad : rays->brad;
+  int rc = validate_rad(ctx, cfg, in, &view, flux ? flux : out, out, /*rays=*/true);
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  return run_solve(ctx, status, stream, "hd_solve_rays", [&](int*& st, hipStream_t s) {
+    return rad_enqueue(ctx, cfg, in, &view, rays, flux, rad, st, s);
   });
 }
 

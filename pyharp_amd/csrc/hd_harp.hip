@@ -454,6 +454,20 @@ int hd_band_flux(const double* flux, const double* weight, int nwave, int ncol, 
   return hd::launched("hd_band_flux");
 }
 
+int hd_band_sum(const double* x, const double* weight, int nwave, long n, double* out,
+                void* stream_) {
+  if (nwave < 0 || n < 0) return hd::set_global_error(HD_EINVAL, "hd_band_sum: bad sizes");
+  if (n == 0) return HD_OK;
+  if ((nwave > 0 && (!x || !weight)) || !out)
+    return hd::set_global_error(HD_EINVAL, "hd_band_sum: null array");
+  // always a lane per output, one fma per wave in wave order from 0: the sequence of
+  // hd_solve_rays' fused sum (the wave-per-output kernel of hd_band_flux adds in
+  // another order)
+  hipLaunchKernelGGL(hd::hd_band_flux_kernel, dim3(nblk(n, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream_), x, weight, nwave, n, out);
+  return hd::launched("hd_band_sum");
+}
+
 int hd_heating_rate(const double* bflux, const double* dz, const double* rho, double cp,
                     int ncol, int nlyr, double* dTdt, void* stream_) {
   if (ncol < 0 || nlyr < 1 || !(cp > 0.0))

@@ -21,6 +21,8 @@
 //   hd_rad_user_kernel<NN>   per (unit, user angle): source-function integration
 //                            along the ray through every layer       [c_usrint]
 //   hd_rad_azimuth_kernel    uu = sum_m I_m cos(m (phi - phi0))
+//   hd_rad_ray_kernel        paired rays (hd_solve_rays): azimuth sum and TMS/IMS per
+//                            (solve, depth, ray), optional band sum over the waves
 //
 // Formulation: DESIGN.md section 3b, mirrored in numpy by
 // tests/kernel_model_rad.py; oracle: oracle/disort_rad_np.py.
@@ -1165,7 +1167,7 @@ void hd_rad_user_kernel(RadArgs A) {
   const long s = A.s0 + sl;
   const int L = A.nlyr, np = A.nprop, nm = A.nmom;
   const size_t nu = A.nu;
-  const double muu = A.umu[iu];
+  const double muu = user_mu(A, s, iu);
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
   const bool beam = fb > 0.0 && mu0 > 0.0;
@@ -1421,7 +1423,7 @@ void hd_rad_user_map_kernel(RadArgs A) {
   const long s = A.s0 + sl;
   const int L = A.nlyr;
   const size_t nu = A.nu;
-  const double muu = A.umu[iu];
+  const double muu = user_mu(A, s, iu);
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
   const bool beam = fb > 0.0 && mu0 > 0.0;
@@ -1683,26 +1685,15 @@ __device__ double ims_term(const RadArgs& A, long s, int nstr, double ct, double
 // delta-M one (truncated series, omega'), both on the scaled depths, and for
 // downward directions minus the IMS term (ims_term); added to uu
 // ============================================================================
-__global__ __launch_bounds__(256) void hd_rad_tms_kernel(RadArgs A, int nstr) {
-  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)A.ns * A.nphi * A.ntau * A.numu;
-  if (id >= n) return;
-  const int sl = (int)(id % A.ns);
-  long r = id / A.ns;
-  const int iu = (int)(r % A.numu);
-  r /= A.numu;
-  const int lu = (int)(r % A.ntau);
-  const int j = (int)(r / A.ntau);
-  const long s = A.s0 + sl;
-  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
-  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  if (!(fb > 0.0 && mu0 > 0.0)) return;
+// the bracket of the correction at one direction (mu, phi [deg]) and user depth lu of
+// solve s = s0 + sl with a beam (fb > 0, mu0 > 0); the correction is fb/(4 pi) times it
+__device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int lu, double mu,
+                                          double phi, double mu0, double fb, int nstr) {
   const int L = A.nlyr, np = A.nprop, nm = A.nmom;
-  const double mu = A.umu[iu];
   const double ph0 = A.phi0 ? A.phi0[s] : 0.0;
   const double ct = fma(-mu, mu0, sqrt(fmax(0.0, 1.0 - mu * mu)) *
                                       sqrt(fmax(0.0, 1.0 - mu0 * mu0)) *
-                                      cos((A.phi[j] - ph0) * (kPi / 180.0)));
+                                      cos((phi - ph0) * (kPi / 180.0)));
   // user depth -> layer and scaled depth
   const double tu = user_tau(A, lu, sl);
   int lu_l = 0;
@@ -1758,8 +1749,108 @@ __global__ __launch_bounds__(256) void hd_rad_tms_kernel(RadArgs A, int nstr) {
     }
   }
   if (mu < 0.0 && fb > 1.0e-4) acc -= ims_term(A, s, nstr, ct, -mu, mu0, tu, lu_l);  // SECSCA: fbeam > tiny
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void hd_rad_tms_kernel(RadArgs A, int nstr) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = (long)A.ns * A.nphi * A.ntau * A.numu;
+  if (id >= n) return;
+  const int sl = (int)(id % A.ns);
+  long r = id / A.ns;
+  const int iu = (int)(r % A.numu);
+  r /= A.numu;
+  const int lu = (int)(r % A.ntau);
+  const int j = (int)(r / A.ntau);
+  const long s = A.s0 + sl;
+  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
+  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
+  if (!(fb > 0.0 && mu0 > 0.0)) return;
+  const double acc = tms_sum(A, s, sl, lu, A.umu[iu], A.phi[j], mu0, fb, nstr);
   A.uu[(((size_t)s * A.nphi + j) * A.ntau + lu) * A.numu + iu] += fb / (4.0 * kPi) * acc;
 }
+
+// ============================================================================
+// ray epilogue (hd_solve_rays): user angle r of a solve is one outgoing ray with its
+// own cosine and azimuth (shared, or the solve's column's own).  Per (solve, depth,
+// ray): the azimuth sum at the ray's phi and, with corint, the Nakajima-Tanaka
+// correction at the ray's (mu, phi) -- one evaluation per ray where the grid kernels
+// do nphi * numu.  A bad cosine (not finite, 0, |mu| > 1: the user-angle kernels ran
+// on 1 in its place) gives NaN and flags the solve.
+// ============================================================================
+__device__ __forceinline__ double ray_radiance(const RadArgs& A, int sl, int lu, int r,
+                                               int nstr) {
+  const long s = A.s0 + sl;
+  const size_t ro = user_angle(A, s, r);
+  const double mu = A.ray_umu[ro];
+  if (!(mu != 0.0) || !(fabs(mu) <= 1.0)) {
+    if (lu == 0) flag(A, s, kStBadInput);
+    return __builtin_nan("");
+  }
+  const double phi = A.phi[ro];
+  const double ph0 = A.phi0 ? A.phi0[s] : 0.0;
+  const double dphi = (phi - ph0) * (kPi / 180.0);
+  const double* src = A.radm + ((size_t)lu * A.numu + r) * A.nu + sl;
+  double acc = 0.0;
+  for (int m = 0; m < A.nm; ++m) acc = fma(src[(size_t)m * A.ns], cos(m * dphi), acc);
+  if (A.corint && A.tauc) {
+    const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
+    const double fb = A.fbeam ? A.fbeam[s] : 0.0;
+    if (fb > 0.0 && mu0 > 0.0)
+      acc = fma(fb / (4.0 * kPi), tms_sum(A, s, sl, lu, mu, phi, mu0, fb, nstr), acc);
+  }
+  return acc;
+}
+
+// BAND = false: one lane per (solve, depth, ray), solve fastest (the radm reads of a
+// wave are contiguous), rad[s][lu][r] stored.
+// BAND = true: one lane per (column, depth, ray), column fastest; the lane takes the
+// chunk's solves of its column in ascending wave order and carries
+//   brad[c][lu][r] = fma(weight[w], rad[w][c][lu][r], brad[c][lu][r])
+// from 0 at w = 0 on, through memory between chunks: one fma per wave in wave order
+// whatever the chunk size (hd_band_sum's sequence, no atomics); rad stored if given
+template <bool BAND>
+__global__ __launch_bounds__(256) void hd_rad_ray_kernel(RadArgs A, int nstr) {
+  const int nx = BAND ? A.ncol : A.ns;
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long)nx * A.ntau * A.numu) return;
+  const int x = (int)(id % nx);
+  const long q = id / nx;
+  const int r = (int)(q % A.numu);
+  const int lu = (int)(q / A.numu);
+  if constexpr (!BAND) {
+    A.rad[((size_t)(A.s0 + x) * A.ntau + lu) * A.numu + r] = ray_radiance(A, x, lu, r, nstr);
+  } else {
+    int w = (int)((A.s0 - x + A.ncol - 1) / A.ncol);  // first wave with w ncol + x >= s0
+    long s = (long)w * A.ncol + x;
+    const long s1 = A.s0 + A.ns;
+    if (s >= s1) return;  // no solve of this column in the chunk
+    const size_t o = ((size_t)x * A.ntau + lu) * A.numu + r;
+    double acc = w == 0 ? 0.0 : A.brad[o];
+    for (; s < s1; s += A.ncol, ++w) {
+      const double v = ray_radiance(A, (int)(s - A.s0), lu, r, nstr);
+      if (A.rad) A.rad[((size_t)s * A.ntau + lu) * A.numu + r] = v;
+      acc = fma(A.weight[w], v, acc);
+    }
+    A.brad[o] = acc;
+  }
+}
+
+#ifndef HD_RAD_WIDE
+__global__ __launch_bounds__(256) void hd_ray_cosines_kernel(const double* umu, double* out,
+                                                             long n) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double mu = umu[i];
+  out[i] = (mu != 0.0 && fabs(mu) <= 1.0) ? mu : 1.0;
+}
+
+hipError_t launch_ray_cosines(const double* umu, double* out, long n, hipStream_t stream) {
+  hipLaunchKernelGGL(hd_ray_cosines_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     stream, umu, out, n);
+  return hipGetLastError();
+}
+#endif
 
 // ============================================================================
 // host side
@@ -1883,7 +1974,9 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
   // nstr 18..32 with radiances: the team user-angle kernel also forms the layers'
   // homogeneous constants (hd_team_mfma.hip), so the const kernel does not run
   const bool team_user =
-      NN > kMaxRegNN && rad && a.numu <= rad_layer_record_doubles(NN) && !rad_user_rolled();
+      NN > kMaxRegNN && rad && a.numu <= rad_layer_record_doubles(NN) && !rad_user_rolled() &&
+      a.umu_stride == 0;  // a team's four units share one user cosine: per-column rays
+                          // take the one-lane user kernel
   // nstr <= 16 with radiances: the const kernel writes the angle-independent maps and
   // the user angles run hd_rad_user_map_kernel (HD_AB=1 HD_RAD_USER=direct: the
   // per-angle hd_rad_user_kernel)
@@ -1898,8 +1991,9 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
                        dim3(256), 0, st, ac);
   }
   const long nf = (long)a.ns * a.ntau;
-  hipLaunchKernelGGL(hd_rad_flux_kernel<NN>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st,
-                     a);
+  if (a.flux)  // optional along rays only
+    hipLaunchKernelGGL(hd_rad_flux_kernel<NN>, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0,
+                       st, a);
   if (rad) {
     const long nr = (long)a.ns * a.numu;
 #ifndef HD_RAD_WIDE
@@ -1912,6 +2006,16 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
       if (!team_user)
         hipLaunchKernelGGL(hd_rad_user_kernel<NN>, dim3((unsigned)((nr + 63) / 64), (unsigned)a.nm),
                            dim3(64), 0, st, a);
+    }
+    if (a.ray_umu) {
+      const long ny = (long)a.ntau * a.numu;
+      if (a.brad)
+        hipLaunchKernelGGL(hd_rad_ray_kernel<true>, dim3((unsigned)((a.ncol * ny + 255) / 256)),
+                           dim3(256), 0, st, a, 2 * NN);
+      else
+        hipLaunchKernelGGL(hd_rad_ray_kernel<false>, dim3((unsigned)((a.ns * ny + 255) / 256)),
+                           dim3(256), 0, st, a, 2 * NN);
+      return;
     }
     const long na = (long)a.ns * a.nphi * a.ntau * a.numu;
     hipLaunchKernelGGL(hd_rad_azimuth_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0,

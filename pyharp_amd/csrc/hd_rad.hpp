@@ -75,6 +75,15 @@ struct RadArgs {
   // user-angle integration runs hd_rad_user_map_kernel
   int umap;
   double* sink;  // team kernels: target of the stores a lane does not own (>= 64 doubles)
+  // paired rays (hd_solve_rays): user angle iu is ray iu, umu/phi hold one (cosine,
+  // azimuth) pair per ray and hd_rad_ray_kernel replaces the azimuth and TMS kernels
+  int umu_stride;  // 0: umu (rays: and phi) shared by every column -- the grid path;
+                   // numu: [ncol][numu], column = (s0 + sl) % ncol
+  const double* ray_umu;  // rays: the caller's cosines as given (umu holds them with the
+                          // bad ones replaced by 1); null = the grid path
+  const double* weight;   // rays: [nwave] band weights or null
+  double* rad;            // rays: [S][ntau][numu] or null
+  double* brad;           // rays: [ncol][ntau][numu] or null (needs weight)
 };
 
 // int_{t1}^{t2} a exp(-c (t - tref)) exp(-(t - t1)/mu) dt/mu, t1 = evaluation
@@ -120,11 +129,25 @@ __device__ __forceinline__ double user_tau(const RadArgs& A, int lu, int sl) {
   return A.utau ? A.utau[lu] : A.taus[(size_t)lu * A.ns + sl];
 }
 
+// index of user angle iu of solve s in umu (rays: and in phi): the shared list, or the
+// list of the solve's column -- s, not the chunk-local sl: a chunk may start mid-wave
+__device__ __forceinline__ size_t user_angle(const RadArgs& A, long s, int iu) {
+  // stride 0 (uniform across the launch): no integer division on the grid path
+  return A.umu_stride ? (size_t)(s % A.ncol) * A.umu_stride + iu : (size_t)iu;
+}
+__device__ __forceinline__ double user_mu(const RadArgs& A, long s, int iu) {
+  return A.umu[user_angle(A, s, iu)];
+}
+
 hipError_t upload_rad_tables(const QuadHost* per_nn);  // nn 1..kRadMaxNN
 // tauc/planck prologue must have run (launch_prologue) for the chunk's solves;
 // radiances = false: fluxes at the user depths only (mode 0, no uu)
 hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_t stream);
 size_t rad_scratch_doubles_per_unit(int nn, int nlyr);
+// rays: out[i] = umu[i], or 1 where umu[i] is not a valid user cosine (not finite, 0 or
+// |umu| > 1), so the user-angle kernels never see such a value; hd_rad_ray_kernel reads
+// the caller's array, answers a bad ray with NaN and flags its solves
+hipError_t launch_ray_cosines(const double* umu, double* out, long n, hipStream_t stream);
 // nstr 18..32: the adding sweep + back-substitution on the team layout with the
 // dense products on FP64 MFMA, four units per wave (hd_team_mfma.hip)
 hipError_t launch_rad_team_sweep(int nn, const RadArgs& a, hipStream_t stream);

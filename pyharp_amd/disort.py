@@ -30,6 +30,8 @@ the built library, ``forward`` raises.
 
 from __future__ import annotations
 
+import math
+import re
 import threading
 from typing import Dict, Optional
 
@@ -114,6 +116,36 @@ def night_side_beam(bc: Dict[str, torch.Tensor], mode: str = "dark",
         fb, mu = torch.broadcast_tensors(fb, mu)
         out["umu0"] = torch.where(fb > 0.0, torch.clamp(mu, min=umu0_min), mu)
     return out
+
+
+_DIRECTION = re.compile(r"\(\s*([^\s,()]+)\s*,\s*([^\s,()]+)\s*\)")
+
+
+def parse_radiation_directions(s: str):
+    """harp's ``outdirs`` string, ``"(zenith,azimuth) (zenith,azimuth) ..."`` with both
+    angles in degrees (RadiationOptions / RadiationBandOptions, src/radiation/
+    radiation.hpp:31, radiation_band.hpp:30), as the ``umu`` / ``phi`` arguments of
+    ``Disort.forward_rays``: two float64 tensors (nray,), ``mu = cos(zenith)`` and the
+    azimuth in DEGREES.  The reference's parser returns one float32 (nray, 2) tensor
+    with the azimuth converted to radians; cdisort and this library take phi in
+    degrees, and float32 would cost the cosine its last nine digits.  A string that is
+    not a whitespace-separated list of ``(number,number)`` pairs raises ValueError."""
+    if not isinstance(s, str):
+        raise ValueError(f"parse_radiation_directions: expected a string, got {type(s).__name__}")
+    pairs = _DIRECTION.findall(s)
+    if not pairs or _DIRECTION.sub("", s).strip():
+        raise ValueError(f"parse_radiation_directions: {s!r} is not a list of "
+                         "'(zenith,azimuth)' pairs")
+    try:
+        zen = [float(a) for a, _ in pairs]
+        azi = [float(b) for _, b in pairs]
+    except ValueError:
+        raise ValueError(f"parse_radiation_directions: {s!r} holds a pair that is not two "
+                         "numbers") from None
+    if not all(math.isfinite(v) for v in zen + azi):
+        raise ValueError(f"parse_radiation_directions: {s!r} holds a non-finite angle")
+    mu = torch.tensor([math.cos(math.radians(z)) for z in zen], dtype=torch.float64)
+    return mu, torch.tensor(azi, dtype=torch.float64)
 
 
 def _beam_hint(bc) -> str:
@@ -328,10 +360,140 @@ class Disort(RTSolver):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
             raise
 
-    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None, flx=False):
+    def forward_rays(self, prop: torch.Tensor, bc: Optional[Dict[str, torch.Tensor]] = None,
+                     temf: Optional[torch.Tensor] = None, *, umu: torch.Tensor,
+                     phi: torch.Tensor, out: Optional[torch.Tensor] = None,
+                     flux: Optional[torch.Tensor] = None,
+                     status: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Radiances (nwave, ncol, ntau, nray) along nray paired outgoing directions
+        (hd_solve_rays): ``umu`` / ``phi`` are float64 tensors (nray,) -- shared by every
+        column -- or (ncol, nray) -- each column's own rays; umu the polar cosine
+        (nonzero, > 0 upward), phi the azimuth in DEGREES.  This is harp's ``outdirs``
+        list (``parse_radiation_directions``) evaluated exactly at every ray, where the
+        legacy driver interpolated a grid solve (rt_solver_disort.cpp_:210-286).  Needs a
+        module without ``onlyfl``; depths are ``user_tau`` with ``usrtau``, else the
+        layer boundaries; the intensity correction follows the flags; the options'
+        ``user_mu`` / ``user_phi`` are not used.  ``flux`` (nwave, ncol, ntau, 2), if
+        given, receives the fluxes at those depths.  CPU inputs (prop, bc, temf, umu, phi)
+        are staged with torch copies and the result comes back on the CPU; caller-supplied
+        ``out`` / ``flux`` / ``status`` buffers are written by the device and must be on the
+        solve device (``cuda:<options.device()>`` for CPU inputs), as for ``forward``.  A ray with umu = 0, |umu| > 1 or
+        a non-finite umu fails its column's solves (HD_STATUS_BAD_INPUT) and is NaN."""
+        try:
+            return self._forward_rays(prop, bc, temf, umu, phi, out, flux, status, None)
+        except RuntimeError as err:
+            if "at least one solve failed" in str(err) and _beam_hint(bc):
+                raise RuntimeError(str(err) + _beam_hint(bc)) from err
+            raise
+
+    def forward_rays_band(self, prop: torch.Tensor,
+                          bc: Optional[Dict[str, torch.Tensor]] = None,
+                          temf: Optional[torch.Tensor] = None, *, umu: torch.Tensor,
+                          phi: torch.Tensor, weights: torch.Tensor,
+                          out: Optional[torch.Tensor] = None,
+                          rad: Optional[torch.Tensor] = None,
+                          flux: Optional[torch.Tensor] = None,
+                          status: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The band radiance (ncol, ntau, nray) = sum_w weights[w] rad_w of
+        ``forward_rays``, with the sum fused into the solve (the legacy driver's
+        ``btoa(n) += wght[b] * toa(b, n)``).  Per-wave radiances are stored only if
+        ``rad`` (nwave, ncol, ntau, nray) is given.  One fma per wave in wave order, no
+        atomics: bitwise equal to ``spectral.band_rad(forward_rays(...), weights)``."""
+        try:
+            return self._forward_rays(prop, bc, temf, umu, phi, rad, flux, status,
+                                      (weights, out))
+        except RuntimeError as err:
+            if "at least one solve failed" in str(err) and _beam_hint(bc):
+                raise RuntimeError(str(err) + _beam_hint(bc)) from err
+            raise
+
+    def _forward_rays(self, prop, bc, temf, umu, phi, rad, flux, status, band):
+        import ctypes
+        who = "Disort.forward_rays" + ("_band" if band is not None else "")
+        ds = self.options.ds()
+        f64 = torch.float64
+        if self.onlyfl:
+            raise RuntimeError(f"{who}: radiances are off (clear the 'onlyfl' flag)")
+        if prop.dim() != 4:
+            raise RuntimeError(f"{who}: prop must be (nwave, ncol, nlyr, nprop), got "
+                               f"{tuple(prop.shape)}")
+        nwave, ncol = prop.shape[0], prop.shape[1]
+        for name, t in (("umu", umu), ("phi", phi)):
+            if not isinstance(t, torch.Tensor) or t.dtype != f64:
+                raise RuntimeError(f"{who}: {name} must be a float64 tensor")
+        if umu.dim() not in (1, 2) or umu.shape[-1] < 1 or \
+                (umu.dim() == 2 and umu.shape[0] != ncol):
+            raise RuntimeError(f"{who}: umu must be (nray,) or (ncol, nray) = ({ncol}, nray), "
+                               f"got {tuple(umu.shape)}")
+        if phi.shape != umu.shape:
+            raise RuntimeError(f"{who}: phi {tuple(phi.shape)} must have umu's shape "
+                               f"{tuple(umu.shape)}")
+        if phi.device != umu.device:
+            raise RuntimeError(f"{who}: umu and phi must be on one device")
+        nray = umu.shape[-1]
+        if band is not None:
+            wts = torch.as_tensor(band[0], dtype=f64).reshape(-1)
+            if wts.numel() != nwave:
+                raise RuntimeError(f"{who}: {wts.numel()} weights for {nwave} waves")
+        bc = {} if bc is None else bc
+        nwave, ncol, nlyr, nprop, in_dev, dev = self._check_inputs(prop, bc, temf)
+        cfg, inp, keep = self._stage(prop, bc, temf, dev)
+        ntau = ds.ntau
+
+        def given(t, shape, name):
+            if t is not None and (t.device != dev or t.dtype != f64 or not t.is_contiguous()
+                                  or tuple(t.shape) != shape):
+                raise RuntimeError(f"{who}: {name} must be a contiguous float64 tensor of "
+                                   f"shape {shape} on {dev}")
+            return t
+
+        rshape = (nwave, ncol, ntau, nray)
+        given(rad, rshape, "rad" if band is not None else "out")
+        given(flux, (nwave, ncol, ntau, 2), "flux")
+        if status is not None and (status.device != dev or status.dtype != torch.int32
+                                   or not status.is_contiguous()
+                                   or status.numel() < nwave * ncol):
+            raise RuntimeError(f"{who}: status must be a contiguous int32 tensor of "
+                               f">= {nwave * ncol} elements on {dev}")
+        brad = None
+        if band is not None:
+            brad = given(band[1], (ncol, ntau, nray), "out")
+            if brad is None:
+                brad = torch.empty((ncol, ntau, nray), dtype=f64, device=dev)
+            wts = wts.to(dev).contiguous()
+            keep.append(wts)
+        elif rad is None:
+            rad = torch.empty(rshape, dtype=f64, device=dev)
+        mu_d, ph_d = umu.to(dev).contiguous(), phi.to(dev).contiguous()
+        keep += [mu_d, ph_d]
+        phi0 = None
+        if bc.get("phi0") is not None:
+            phi0 = torch.as_tensor(bc["phi0"], dtype=f64).expand((nwave, ncol)).to(dev)
+            phi0 = phi0.contiguous()
+            keep.append(phi0)
+        ut = (ctypes.c_double * max(1, len(ds.utau)))(*ds.utau)
+        rays = _lib.HdRays(nray=nray, per_column=int(umu.dim() == 2), umu=mu_d.data_ptr(),
+                           phi=ph_d.data_ptr(), ntau=len(ds.utau) if self.usrtau else 0,
+                           utau=ctypes.cast(ut, ctypes.c_void_p),
+                           phi0=phi0.data_ptr() if phi0 is not None else None,
+                           corint=int(self.corint),
+                           weight=wts.data_ptr() if band is not None else None,
+                           brad=brad.data_ptr() if brad is not None else None)
+        stream = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            _context(dev.index).solve_rays(
+                cfg, inp, rays, flux.data_ptr() if flux is not None else None,
+                rad.data_ptr() if rad is not None else None,
+                status.data_ptr() if status is not None else None, stream.cuda_stream)
+        del keep
+        res = brad if band is not None else rad
+        return res.to(in_dev) if in_dev.type != "cuda" else res
+
+    def _check_inputs(self, prop, bc, temf):
+        """The shape and option checks every forward_* shares, before anything is staged;
+        returns (nwave, ncol, nlyr, nprop, the input's device, the solve's device)."""
         op = self.options
         ds = op.ds()
-        bc = {} if bc is None else bc
         if prop.dim() != 4:
             raise RuntimeError(f"Disort.forward: prop must be (nwave, ncol, nlyr, nprop), got "
                                f"{tuple(prop.shape)}")
@@ -353,13 +515,15 @@ class Disort(RTSolver):
                                "CPU path)")
         in_dev = prop.device
         dev = in_dev if in_dev.type == "cuda" else torch.device("cuda", int(op.device()))
+        return nwave, ncol, nlyr, nprop, in_dev, dev
+
+    def _stage(self, prop, bc, temf, dev):
+        """The inputs as contiguous float64 tensors on ``dev`` and the library's view of
+        them: (hd_config, hd_inputs, the tensors to keep alive over the call)."""
+        op = self.options
+        ds = op.ds()
+        nwave, ncol, nlyr, nprop = prop.shape
         f64 = torch.float64
-        if (in_dev.type != "cuda" and not self.radiance and out is None and status is None
-                and not flx):
-            # pydisort's CPU-tensor contract: the library's host-array entry points
-            # (hd_solve_host / hd_solve_band_host) copy the arrays over in pieces
-            # beside the solve of the previous piece
-            return self._forward_host(prop, bc, temf, band, dev, nwave, ncol, nlyr, nprop)
 
         def dev_tensor(x, shape=None):
             if x is None:
@@ -393,6 +557,33 @@ class Disort(RTSolver):
                                torch.tensor(op.wave_upper(), dtype=f64, device=dev))
             wl, wu = self._waves[1], self._waves[2]
             keep += [tf, wl, wu]
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        cfg = _lib.HdConfig(nstr=ds.nstr, nmom=ds.nmom, nlyr=nlyr, nprop=nprop,
+                            flags=_lib.HD_FLAG_LAMBER | _lib.HD_FLAG_ONLYFL |
+                            (_lib.HD_FLAG_PLANCK if self.planck else 0))
+        inp = _lib.HdInputs(nwave=nwave, ncol=ncol, prop=ptr(p),
+                            fbeam=ptr(bct.get("fbeam")), umu0=ptr(bct.get("umu0")),
+                            albedo=ptr(bct.get("albedo")), btemp=ptr(bct.get("btemp")),
+                            ttemp=ptr(bct.get("ttemp")), temis=ptr(bct.get("temis")),
+                            fisot=ptr(bct.get("fisot")), temf=ptr(tf), wave_lower=ptr(wl),
+                            wave_upper=ptr(wu))
+        return cfg, inp, keep
+
+    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None, flx=False):
+        ds = self.options.ds()
+        bc = {} if bc is None else bc
+        nwave, ncol, nlyr, nprop, in_dev, dev = self._check_inputs(prop, bc, temf)
+        f64 = torch.float64
+        if (in_dev.type != "cuda" and not self.radiance and out is None and status is None
+                and not flx):
+            # pydisort's CPU-tensor contract: the library's host-array entry points
+            # (hd_solve_host / hd_solve_band_host) copy the arrays over in pieces
+            # beside the solve of the previous piece
+            return self._forward_host(prop, bc, temf, band, dev, nwave, ncol, nlyr, nprop)
+        cfg, inp, keep = self._stage(prop, bc, temf, dev)
         nlev = ds.ntau if self.radiance else nlyr + 1
         ncomp = NFLX if flx else 2
         if out is None:
@@ -414,15 +605,6 @@ class Disort(RTSolver):
         def ptr(t):
             return t.data_ptr() if t is not None else None
 
-        cfg = _lib.HdConfig(nstr=ds.nstr, nmom=ds.nmom, nlyr=nlyr, nprop=nprop,
-                            flags=_lib.HD_FLAG_LAMBER | _lib.HD_FLAG_ONLYFL |
-                            (_lib.HD_FLAG_PLANCK if self.planck else 0))
-        inp = _lib.HdInputs(nwave=nwave, ncol=ncol, prop=ptr(p),
-                            fbeam=ptr(bct.get("fbeam")), umu0=ptr(bct.get("umu0")),
-                            albedo=ptr(bct.get("albedo")), btemp=ptr(bct.get("btemp")),
-                            ttemp=ptr(bct.get("ttemp")), temis=ptr(bct.get("temis")),
-                            fisot=ptr(bct.get("fisot")), temf=ptr(tf), wave_lower=ptr(wl),
-                            wave_upper=ptr(wu))
         stream = torch.cuda.current_stream(dev)
         if band is not None:
             wts = torch.as_tensor(band[0], dtype=f64).to(dev).reshape(-1).contiguous()

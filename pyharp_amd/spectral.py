@@ -80,6 +80,32 @@ def band_flx(flx: torch.Tensor, weights: torch.Tensor,
     return out
 
 
+def band_rad(x: torch.Tensor, weights: torch.Tensor,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum_w weights[w] x[w] for any per-wave field x (nwave, ...), e.g. the ray
+    radiances (nwave, ncol, ntau, nray) of Disort.forward_rays: shape x.shape[1:]
+    (hd_band_sum; the legacy driver's ``btoa(n) += wght[b] * toa(b, n)``,
+    rt_solver_disort.cpp_:268-271).  One fma per wave in wave order: bitwise equal to
+    the sum Disort.forward_rays_band fuses into the solve."""
+    f = _dev_f64(x, "band_rad")
+    if f.dim() < 1:
+        raise RuntimeError("band_rad: x must be (nwave, ...)")
+    nwave = f.shape[0]
+    w = torch.as_tensor(weights, dtype=torch.float64).to(f.device).reshape(-1).contiguous()
+    if w.numel() != nwave:
+        raise RuntimeError(f"band_rad: {w.numel()} weights for {nwave} waves")
+    if out is None:
+        out = torch.empty(tuple(f.shape[1:]), dtype=torch.float64, device=f.device)
+    elif (out.device != f.device or out.dtype != torch.float64 or not out.is_contiguous()
+          or out.shape != f.shape[1:]):
+        raise RuntimeError(f"band_rad: out must be a contiguous float64 tensor of shape "
+                           f"{tuple(f.shape[1:])} on {f.device}")
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.load().hd_band_sum(f.data_ptr(), w.data_ptr(), nwave, out.numel(),
+                                           out.data_ptr(), _stream(f.device)))
+    return out
+
+
 def heating_rate(bflux: torch.Tensor, dz: torch.Tensor, rho: torch.Tensor,
                  cp: float) -> torch.Tensor:
     """dT/dt (ncol, nlyr) [K/s] = -(1/(rho c_p)) d(F_up - F_dn)/dz from the band

@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--chunk", type=int, default=0, help="solves per chunk (0: by scratch budget)")
+    ap.add_argument("--dump-uu", default=None, help="save the last step's uu to this .npy")
     a = ap.parse_args()
     from pyharp_amd import Disort, DisortOptions
     dev = torch.device("cuda", 0)
@@ -70,6 +71,8 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     uu = d.get_rad().cpu().numpy()
+    if a.dump_uu:
+        np.save(a.dump_uu, uu)
     # subsample check (oracle: test infrastructure, used here as the checker only)
     from oracle.disort_rad_np import disort_rad_forward
     idx = rng.choice(G * C, 4, replace=False)
