@@ -12,10 +12,11 @@ from .index import (IDFDT, IFLUP, IRFLDIR, IRFLDN, IUAVG, IUAVGDN, IUAVGSO,  # n
 from .rtsolver import RTSolver  # noqa: F401
 from .disort import (Disort, DisortOptions, night_side_beam,  # noqa: F401
                      parse_radiation_directions)
+from .beer_lambert import BeerLambert, BeerLambertOptions  # noqa: F401
 from .layer2level import Layer2LevelOptions, layer2level  # noqa: F401
 from .scattering import PhaseMomentOptions, scattering_moments  # noqa: F401
 
-__all__ = ["Disort", "DisortOptions", "RTSolver", "layer2level", "Layer2LevelOptions",
+__all__ = ["BeerLambert", "BeerLambertOptions", "Disort", "DisortOptions", "RTSolver", "layer2level", "Layer2LevelOptions",
            "IEX", "ISS", "IPM", "IUP", "IDN", "PhaseMomentOptions",
            "scattering_moments", "night_side_beam", "parse_radiation_directions",
            "IRFLDIR", "IRFLDN", "IFLUP", "IDFDT", "IUAVG", "IUAVGDN", "IUAVGUP", "IUAVGSO", "NFLX"]

@@ -14,9 +14,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhdisort.so")
 SOURCES = ["hd_kernels.hip", "hd_team.hip", "hd_team_mfma.hip", "hd_rad.hip", "hd_harp.hip",
-           "hd_api.cpp", "hd_ncread.cpp", "hd_rad_wide.hip"]
-HEADERS = ["hd_device.hpp", "hd_kernels.hpp", "hd_rad.hpp", "hd_team_prims.hpp", os.path.join("..", "..", "include", "hdisort.h"),
+           "hd_api.cpp", "hd_ncread.cpp", "hd_rad_wide.hip", "hd_beer.hip"]
+HEADERS = ["hd_device.hpp", "hd_kernels.hpp", "hd_beer.hpp", "hd_rad.hpp", "hd_team_prims.hpp", os.path.join("..", "..", "include", "hdisort.h"),
            os.path.join("..", "..", "include", "hdharp.h"),
+           os.path.join("..", "..", "include", "hdbeer.h"),
            os.path.join("..", "..", "include", "hdnc.h"),
            os.path.join("..", "..", "include", "harp_amd", "ncread.hpp"),
            os.path.join("..", "..", "include", "harp_amd", "nc4read.hpp")]
@@ -26,7 +27,12 @@ ARCH = os.environ.get("HD_OFFLOAD_ARCH", "gfx950")
 # they are used instead of being hoisted out of its layer loop -- 254 VGPRs and 20 B
 # of scratch at nstr 32 instead of 156 B of spills at the two-waves-per-SIMD cap;
 # the team layer kernel is unchanged (239)
-EXTRA = {"hd_team_mfma.hip": ["-mllvm", "-disable-machine-licm"]}
+EXTRA = {"hd_team_mfma.hip": ["-mllvm", "-disable-machine-licm"],
+         # hd_beer.hip: hoisted out of the layer loops, the constants of exp() and of the
+         # small-x series fill the scalar file beside the quadrature (4 SGPRs per node)
+         # and SGPRs spill into VGPR lanes -- 85-202 VGPRs and a 20 B frame at seven
+         # values of nstr, against 62-179 and no frame with the constants formed in place
+         "hd_beer.hip": ["-mllvm", "-disable-machine-licm"]}
 
 
 def _hipcc() -> str:

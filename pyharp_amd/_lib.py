@@ -36,6 +36,9 @@ HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rf
                  "hd_spherical_flux_correction")
 HD_COORD_WAVELENGTH, HD_COORD_WAVENUMBER = 0, 1
 
+# every symbol include/hdbeer.h declares (the Beer-Lambert solver)
+BEER_EXPORTED = ("hd_beer_flux", "hd_beer_flux_band", "hd_beer_rays")
+
 # every symbol include/hdnc.h declares (netCDF readers, host code)
 NC_EXPORTED = ("hd_nc_open", "hd_nc_close", "hd_nc_dim_len", "hd_nc_var_size",
                "hd_nc_get_var_double")
@@ -80,6 +83,11 @@ class HdRays(ctypes.Structure):
     _fields_ = [("nray", ctypes.c_int), ("per_column", ctypes.c_int), ("umu", _dp), ("phi", _dp),
                 ("ntau", ctypes.c_int), ("utau", _dp), ("phi0", _dp), ("corint", ctypes.c_int),
                 ("weight", _dp), ("brad", _dp)]
+
+
+class HdBeerRays(ctypes.Structure):
+    _fields_ = [("nray", ctypes.c_int), ("per_column", ctypes.c_int), ("umu", _dp),
+                ("alpha", ctypes.c_double), ("weight", _dp), ("brad", _dp)]
 
 
 class HdBand(ctypes.Structure):
@@ -138,6 +146,11 @@ def load(path: str = LIB_PATH):
                                   ctypes.POINTER(HdInputs), ctypes.POINTER(HdRays),
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p]
+    lib.hd_beer_flux.argtypes = lib.hd_solve.argtypes
+    lib.hd_beer_flux_band.argtypes = lib.hd_solve_band.argtypes
+    lib.hd_beer_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                 ctypes.POINTER(HdInputs), ctypes.POINTER(HdBeerRays),
+                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_quadrature.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double)]
     ci, cd = ctypes.c_int, ctypes.c_double
@@ -160,7 +173,7 @@ def load(path: str = LIB_PATH):
     lib.hd_nc_var_size.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
     lib.hd_nc_get_var_double.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p,
                                          ctypes.c_long]
-    for name in EXPORTED + HARP_EXPORTED + NC_EXPORTED:
+    for name in EXPORTED + HARP_EXPORTED + BEER_EXPORTED + NC_EXPORTED:
         getattr(lib, name)
     _lib = lib
     return lib
@@ -271,6 +284,31 @@ class Context:
                                   ctypes.c_void_p(rad_ptr or 0),
                                   ctypes.c_void_p(status_ptr or 0),
                                   ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def beer_flux(self, cfg: HdConfig, inp: HdInputs, flux_ptr: int, status_ptr: int | None,
+                  stream_ptr: int | None):
+        """hd_beer_flux: pure-absorption fluxes in hd_solve's layout."""
+        rc = load().hd_beer_flux(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                 ctypes.c_void_p(flux_ptr), ctypes.c_void_p(status_ptr or 0),
+                                 ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def beer_flux_band(self, cfg: HdConfig, inp: HdInputs, band: HdBand, flux_ptr: int | None,
+                       status_ptr: int | None, stream_ptr: int | None):
+        rc = load().hd_beer_flux_band(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                      ctypes.byref(band), ctypes.c_void_p(flux_ptr or 0),
+                                      ctypes.c_void_p(status_ptr or 0),
+                                      ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def beer_rays(self, cfg: HdConfig, inp: HdInputs, rays: HdBeerRays, rad_ptr: int | None,
+                  status_ptr: int | None, stream_ptr: int | None):
+        """hd_beer_rays: emergent radiances; rad and/or rays.brad."""
+        rc = load().hd_beer_rays(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                 ctypes.byref(rays), ctypes.c_void_p(rad_ptr or 0),
+                                 ctypes.c_void_p(status_ptr or 0),
+                                 ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
 

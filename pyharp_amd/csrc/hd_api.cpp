@@ -19,8 +19,10 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hdbeer.h"
 #include "../../include/hdharp.h"
 #include "../../include/hdisort.h"
+#include "hd_beer.hpp"
 #include "hd_kernels.hpp"
 #include "hd_team_prims.hpp"
 #include "hd_rad.hpp"
@@ -1539,5 +1541,170 @@ int hd_solve_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   });
 }
 
+}  // extern "C"
+
+// ============================================================================
+// Beer-Lambert solver (include/hdbeer.h; kernels in hd_beer.hip)
+// ============================================================================
+namespace {
+
+constexpr long kBeerChunk = 262144;  // solves per automatic chunk
+
+// flux given / band given: hd_beer_flux(_band); rays given: hd_beer_rays (out = rad)
+int beer_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* out,
+                 const hd_band* band, const struct hd_beer_rays* rays, int*& status,
+                 hipStream_t stream, const char* who) {
+  int rc = HD_OK;
+  const long nsolve = (long)in->nwave * in->ncol;
+  const int nn = cfg->nstr / 2;
+  const int nlyr = cfg->nlyr;
+  const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
+  const bool sync = status == nullptr;
+  const size_t m = rays ? (size_t)rays->nray : 2 * (size_t)(nlyr + 1);  // values per solve
+  const double* weight = rays ? rays->weight : (band ? band->weight : nullptr);
+  double* bout = rays ? rays->brad : (band ? band->bflux : nullptr);
+  const long chunk = std::min(nsolve, ctx->chunk > 0 ? ctx->chunk : kBeerChunk);
+  // scratch of one chunk: planck [nlyr+3] | xsurf (rays) | per-wave values (band sum
+  // without a caller buffer for them)
+  const size_t n_planck = planck ? (size_t)(nlyr + 3) * chunk : 0;
+  const size_t n_xsurf = rays ? (size_t)chunk : 0;
+  const size_t n_local = out ? 0 : m * (size_t)chunk;
+  rc = ensure_scratch(ctx, std::max<size_t>(n_planck + n_xsurf + n_local, 1));
+  if (rc) return rc;
+  if (sync) {
+    rc = ensure_status(ctx, (size_t)nsolve);
+    if (rc) return rc;
+    status = ctx->status;
+  }
+  HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
+  HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
+  if (bout) HD_HIP(ctx, hipMemsetAsync(bout, 0, sizeof(double) * in->ncol * m, stream));
+  double* planck_q = planck ? ctx->scratch : nullptr;
+  double* xsurf_q = ctx->scratch + n_planck;
+  double* local_q = ctx->scratch + n_planck + n_xsurf;
+  const hd::QuadHost& q = quad_host()[nn - 1];
+  for (long s0 = 0; s0 < nsolve; s0 += chunk) {
+    const int nsc = (int)std::min(chunk, nsolve - s0);
+    if (planck) {
+      hd::PlanckArgs pa{};
+      pa.temf = in->temf;
+      pa.btemp = in->btemp;
+      pa.ttemp = in->ttemp;
+      pa.temis = in->temis;
+      pa.wlo = in->wave_lower;
+      pa.whi = in->wave_upper;
+      pa.out = planck_q;
+      pa.s0 = s0;
+      pa.nsc = nsc;
+      pa.ncol = in->ncol;
+      pa.nlyr = nlyr;
+      hd::launch_prologue(&pa, nullptr, stream);
+    }
+    double* vals = out ? out + (size_t)s0 * m : local_q;  // the chunk's per-wave values
+    hd::BeerArgs a{};
+    a.prop = in->prop;
+    a.fbeam = in->fbeam;
+    a.umu0 = in->umu0;
+    a.albedo = in->albedo;
+    a.fisot = in->fisot;
+    a.planckv = planck_q;
+    a.flux = rays ? nullptr : vals;
+    a.xsurf = rays ? xsurf_q : nullptr;
+    a.status = status;
+    a.anyerr = ctx->anyerr;
+    a.s0 = s0;
+    a.nsc = nsc;
+    a.nlyr = nlyr;
+    a.nprop = cfg->nprop;
+    for (int i = 0; i < nn; ++i) {
+      a.rmu[i] = 1.0 / q.mu[i];
+      a.wmu[i] = q.w[i] * q.mu[i];
+    }
+    hipError_t e;
+    if (!rays) {
+      e = hd::launch_beer_flux(nn, a, stream);
+    } else {
+      e = hd::launch_beer_surface(nn, a, stream);
+      if (e == hipSuccess) {
+        hd::BeerRayArgs r{};
+        r.prop = in->prop;
+        r.albedo = in->albedo;
+        r.fisot = in->fisot;
+        r.planckv = planck_q;
+        r.xsurf = xsurf_q;
+        r.umu = rays->umu;
+        r.rad = vals;
+        r.status = status;
+        r.anyerr = ctx->anyerr;
+        r.s0 = s0;
+        r.nsc = nsc;
+        r.ncol = in->ncol;
+        r.nlyr = nlyr;
+        r.nprop = cfg->nprop;
+        r.nray = rays->nray;
+        r.per_column = rays->per_column;
+        r.alpha = rays->alpha;
+        e = hd::launch_beer_rays(r, stream);
+      }
+    }
+    if (e == hipSuccess && bout)
+      e = hd::launch_beer_band_acc(vals, weight, bout, s0, nsc, in->ncol, (long)m, stream);
+    if (e != hipSuccess)
+      return fail(ctx, HD_EHIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+  }
+  return HD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hd_beer_flux(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
+                 int* status, void* stream) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_flux: null context");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = validate(ctx, cfg, in, flux, "hd_beer_flux");
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  return run_solve(ctx, status, stream, "hd_beer_flux", [&](int*& st, hipStream_t s) {
+    return beer_enqueue(ctx, cfg, in, flux, nullptr, nullptr, st, s, "hd_beer_flux");
+  });
+}
+
+int hd_beer_flux_band(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                      const hd_band* band, double* flux, int* status, void* stream) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_flux_band: null context");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!band || !band->weight || !band->bflux)
+    return fail(ctx, HD_EINVAL, "hd_beer_flux_band: band weights and bflux are required");
+  int rc = validate(ctx, cfg, in, flux ? flux : band->bflux, "hd_beer_flux_band");
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  return run_solve(ctx, status, stream, "hd_beer_flux_band", [&](int*& st, hipStream_t s) {
+    return beer_enqueue(ctx, cfg, in, flux, band, nullptr, st, s, "hd_beer_flux_band");
+  });
+}
+
+int hd_beer_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                 const struct hd_beer_rays* rays, double* rad, int* status, void* stream) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_rays: null context");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!rays) return fail(ctx, HD_EINVAL, "hd_beer_rays: null ray config");
+  if (!rad && !rays->brad)
+    return fail(ctx, HD_EINVAL, "hd_beer_rays: rad and brad both NULL: nothing to compute");
+  if (rays->brad && !rays->weight) return fail(ctx, HD_EINVAL, "hd_beer_rays: brad needs weight");
+  if (rays->nray < 1 || !rays->umu)
+    return fail(ctx, HD_EINVAL, "hd_beer_rays: rays need nray >= 1 and umu");
+  if (rays->per_column != 0 && rays->per_column != 1)
+    return fail(ctx, HD_EINVAL, "hd_beer_rays: per_column=%d must be 0 or 1", rays->per_column);
+  if (!(rays->alpha >= 0.0) || !std::isfinite(rays->alpha))
+    return fail(ctx, HD_EINVAL, "hd_beer_rays: alpha=%g must be finite and >= 0", rays->alpha);
+  int rc = validate(ctx, cfg, in, rad ? rad : rays->brad, "hd_beer_rays");
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  return run_solve(ctx, status, stream, "hd_beer_rays", [&](int*& st, hipStream_t s) {
+    return beer_enqueue(ctx, cfg, in, rad, nullptr, rays, st, s, "hd_beer_rays");
+  });
+}
 
 }  // extern "C"
