@@ -223,60 +223,13 @@ int ensure_rad_tables(hd_context* ctx) {
   return HD_OK;
 }
 
-constexpr long kRegChunkMax = 40960;  // the register path's largest automatic chunk
+using hd::auto_chunk;
+using hd::max_auto_chunk;
 
-// team path: bytes of scratch for the two chunks in flight (the per-solve size counts
-// both) within a 16 GB budget
-long team_chunk_target(int nn, int nlyr, bool planck) {
-  const double budget = 16.0 * 1024.0 * 1024.0 * 1024.0;
-  const double per = 8.0 * (double)hd::scratch_doubles_per_solve(nn, nlyr, planck);
-  return std::min<long>(262144, std::max<long>(16384, (long)(budget / per)));
-}
-
-long auto_chunk(long nsolve, int nn, int nlyr, bool planck) {
-  // NN <= 8: the sweep runs one lane per solve at one wave per SIMD (its register
-  // file is full) and cannot share a SIMD with the layer kernel.  Chunks of 32 000-
-  // 40 000 solves (500-625 sweep waves) leave 40-50 % of the SIMDs to the next chunk's
-  // layer kernel while a sweep runs, instead of the 1 024 waves of a 65 536-solve chunk
-  // that take every SIMD: C4 12.80 -> 13.35 M solves/s at 20 chunks of 32 000 (16 of
-  // 40 000: 13.27; 24-28 chunks: 12.96-13.03).  With fewer than five chunks the
-  // pipeline's fill and drain dominate and the larger chunk wins: the 8-GPU rank shape
-  // (80 000) runs 2 x 40 000 at 12.15 M, 3 x 26 667 at 11.78
-  // (profiles/r05/chunk_sweep.txt).
-  // NN > 8: one 16-lane team per solve; chunks bounded by a scratch budget
-  // (the rest of the 288 GB stays the caller's).
-  long target;
-  if (nn <= hd::kMaxRegNN) {
-    target = (nsolve + 32767) / 32768 >= 5 ? 32768 : kRegChunkMax;
-  } else {
-    target = team_chunk_target(nn, nlyr, planck);
-  }
-  // (team path: a call that fits one chunk stays one chunk.  Split in two, the 8-GPU
-  // C5 rank shape -- 8 000 solves -- ran 1.155 M solves/s against 1.268 M: a 4 000-solve
-  // layer kernel takes 2.57 ms alone and 3.63 ms beside the first chunk's sweep,
-  // against 4.59 ms for all 8 000, profiles/r05/c5_rank_shape.txt)
-  if (nsolve <= target) return nsolve;
-  const long n = (nsolve + target - 1) / target;
-  return (nsolve + n - 1) / n;
-}
-
-// The largest chunk auto_chunk gives any call of at most nsolve solves (the chunk
-// size is not monotone in nsolve: 163 840 solves run in chunks of 32 768, 80 000 in
-// chunks of 40 000), so hd_context_reserve(nsolve) covers every smaller call too.
-// hd_solve_band without caller fluxes on the register path, when the call runs as the
-// three-stream pipeline of five or more automatic chunks (the 32 768-solve regime): the
-// row-major chunks of hd_solve into a per-g flux buffer of the context, then
-// hd_band_flux.  C4: 14.80-14.92 M solves/s against 14.33-14.45 M for the column-major
-// fused epilogue on one box (profiles/r06/fuse_ab.txt); the 8-GPU rank shape (two
-// chunks) is equal and the small shapes keep the fused epilogue.
+// hd_solve_band's row-major route (hd_plan.hpp: band_rowmajor_size) under the context's
+// switches
 bool band_rowmajor(const hd_context* ctx, int nn, long nsolve) {
-  return nn <= hd::kMaxRegNN && ctx->chunk <= 0 && !ctx->band_cmaj && !ctx->column &&
-         (nsolve + 32767) / 32768 >= 5;
-}
-
-long max_auto_chunk(long nsolve, int nn, int nlyr, bool planck) {
-  const long cap = nn <= hd::kMaxRegNN ? kRegChunkMax : team_chunk_target(nn, nlyr, planck);
-  return std::min(nsolve, cap);
+  return ctx->chunk <= 0 && !ctx->band_cmaj && !ctx->column && hd::band_rowmajor_size(nn, nsolve);
 }
 
 // the last solve that used the context's buffers has finished (before a free)
@@ -284,65 +237,58 @@ void drain(hd_context* ctx) {
   if (ctx->done_valid) (void)hipEventSynchronize(ctx->ev_done);
 }
 
-// Growing a buffer frees the old one, which a captured graph may still point at,
-// and a free/malloc cannot be captured: during capture growth is an error (size
-// the context first with hd_context_reserve, or run the call once eagerly).
-int ensure_scratch(hd_context* ctx, size_t ndoubles) {
-  if (ctx->scratch_doubles >= ndoubles) return HD_OK;
-  if (ctx->capturing)
-    return fail(ctx, HD_EINVAL,
-                "hd_solve: scratch must grow to %zu bytes inside a stream capture; size the "
-                "context first (hd_context_reserve, or one eager call of the same shape)",
-                ndoubles * sizeof(double));
+// The messages of one of the context's device buffers, printf formats over (entry
+// point, bytes).  capture null: a buffer no capturing call reaches.
+struct BufText {
+  const char* capture;
+  const char* nomem;
+};
+constexpr BufText kScratchText{
+    "%s: scratch must grow to %zu bytes inside a stream capture; size the "
+    "context first (hd_context_reserve, or one eager call of the same shape)",
+    "%s: cannot allocate %zu bytes of scratch"};
+constexpr BufText kPfluxText{
+    "%s: the per-g flux buffer must grow to %zu bytes inside a stream "
+    "capture; size the context first (hd_context_reserve, or one eager call of the "
+    "same shape)",
+    "%s: cannot allocate %zu bytes of per-g fluxes"};
+constexpr BufText kStatusText{
+    "%s: the status buffer must grow inside a stream capture; pass a status "
+    "buffer or size the context first (hd_context_reserve)",
+    "%s: cannot allocate status buffer"};
+constexpr BufText kStageText{nullptr, "%s: cannot allocate %zu bytes of staging"};
+constexpr BufText kGridText{nullptr, "%s: cannot allocate %zu bytes of user grid"};
+
+// The context's device buffers only grow.  Growing a buffer frees the old one, which a
+// captured graph may still point at, and a free/malloc cannot be captured: during
+// capture growth is an error (size the context first with hd_context_reserve, or run
+// the call once eagerly).  who: the entry point in the messages.
+template <class T>
+int ensure(hd_context* ctx, const char* who, const BufText& text, T*& p, size_t& len, size_t n) {
+  if (len >= n) return HD_OK;
+  if (ctx->capturing && text.capture) return fail(ctx, HD_EINVAL, text.capture, who, n * sizeof(T));
   drain(ctx);
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
-  ctx->scratch = nullptr;
-  ctx->scratch_doubles = 0;
-  if (hipMalloc(&ctx->scratch, ndoubles * sizeof(double)) != hipSuccess) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  len = 0;
+  if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(ctx, HD_ENOMEM, "hd_solve: cannot allocate %zu bytes of scratch",
-                ndoubles * sizeof(double));
+    return fail(ctx, HD_ENOMEM, text.nomem, who, n * sizeof(T));
   }
-  ctx->scratch_doubles = ndoubles;
+  len = n;
   return HD_OK;
 }
-
+int ensure_scratch(hd_context* ctx, const char* who, size_t ndoubles) {
+  return ensure(ctx, who, kScratchText, ctx->scratch, ctx->scratch_doubles, ndoubles);
+}
 int ensure_pflux(hd_context* ctx, size_t ndoubles) {
-  if (ctx->pflux_doubles >= ndoubles) return HD_OK;
-  if (ctx->capturing)
-    return fail(ctx, HD_EINVAL,
-                "hd_solve_band: the per-g flux buffer must grow to %zu bytes inside a stream "
-                "capture; size the context first (hd_context_reserve, or one eager call of the "
-                "same shape)", ndoubles * sizeof(double));
-  drain(ctx);
-  if (ctx->pflux) (void)hipFree(ctx->pflux);
-  ctx->pflux = nullptr;
-  ctx->pflux_doubles = 0;
-  if (hipMalloc(&ctx->pflux, ndoubles * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, HD_ENOMEM, "hd_solve_band: cannot allocate %zu bytes of per-g fluxes",
-                ndoubles * sizeof(double));
-  }
-  ctx->pflux_doubles = ndoubles;
-  return HD_OK;
+  return ensure(ctx, "hd_solve_band", kPfluxText, ctx->pflux, ctx->pflux_doubles, ndoubles);
 }
-
-int ensure_status(hd_context* ctx, size_t n) {
-  if (ctx->status_len >= n) return HD_OK;
-  if (ctx->capturing)
-    return fail(ctx, HD_EINVAL,
-                "hd_solve: the status buffer must grow inside a stream capture; pass a status "
-                "buffer or size the context first (hd_context_reserve)");
-  drain(ctx);
-  if (ctx->status) (void)hipFree(ctx->status);
-  ctx->status = nullptr;
-  ctx->status_len = 0;
-  if (hipMalloc(&ctx->status, std::max<size_t>(n, 1) * sizeof(int)) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(ctx, HD_ENOMEM, "hd_solve: cannot allocate status buffer");
-  }
-  ctx->status_len = n;
-  return HD_OK;
+// the context's own per-solve status (the caller passed none)
+int own_status(hd_context* ctx, const char* who, size_t nsolve, int*& status) {
+  const int rc = ensure(ctx, who, kStatusText, ctx->status, ctx->status_len, nsolve);
+  status = ctx->status;
+  return rc;
 }
 
 // fold every recorded (K1 start, K1 end, K2 start, K2 end) quadruple into the totals
@@ -392,21 +338,32 @@ int leave(hd_context* ctx, hipStream_t stream, bool capturing) {
   return HD_OK;
 }
 
-// who: the name of the entry point in the messages
-int validate(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, const double* flux,
-             const char* who = "hd_solve") {
+// the stream count and the layer count of a config
+enum ConfigCheck { kConfigOk, kConfigNstr, kConfigNlyr };
+ConfigCheck check_config(const hd_config* cfg) {
+  if (cfg->nstr < 2 || cfg->nstr % 2 || cfg->nstr / 2 > hd::kMaxNN) return kConfigNstr;
+  return cfg->nlyr < 1 ? kConfigNlyr : kConfigOk;
+}
+
+// who: the name of the entry point in the messages.  out: the output array; out_optional:
+// the entry point has another output it has checked itself, this one may be null
+int validate(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, const double* out,
+             const char* who = "hd_solve", bool out_optional = false) {
   if (!cfg || !in) return fail(ctx, HD_EINVAL, "%s: null config/inputs", who);
-  if (cfg->nstr < 2 || cfg->nstr % 2 || cfg->nstr / 2 > hd::kMaxNN)
-    return fail(ctx, HD_EINVAL, "%s: nstr=%d must be even and in [2, %d]", who, cfg->nstr,
-                2 * hd::kMaxNN);
-  if (cfg->nlyr < 1) return fail(ctx, HD_EINVAL, "%s: nlyr=%d < 1", who, cfg->nlyr);
+  switch (check_config(cfg)) {
+    case kConfigNstr:
+      return fail(ctx, HD_EINVAL, "%s: nstr=%d must be even and in [2, %d]", who, cfg->nstr,
+                  2 * hd::kMaxNN);
+    case kConfigNlyr: return fail(ctx, HD_EINVAL, "%s: nlyr=%d < 1", who, cfg->nlyr);
+    case kConfigOk: break;
+  }
   if (cfg->nprop < 1) return fail(ctx, HD_EINVAL, "%s: nprop=%d < 1", who, cfg->nprop);
   if (cfg->nmom < 0) return fail(ctx, HD_EINVAL, "%s: nmom=%d < 0", who, cfg->nmom);
   if (cfg->flags & ~(HD_FLAG_LAMBER | HD_FLAG_PLANCK | HD_FLAG_ONLYFL))
     return fail(ctx, HD_EINVAL, "%s: unsupported flags 0x%x", who, cfg->flags);
   if (in->nwave < 0 || in->ncol < 0)
     return fail(ctx, HD_EINVAL, "%s: negative nwave/ncol", who);
-  if ((long)in->nwave * in->ncol > 0 && (!in->prop || !flux))
+  if ((long)in->nwave * in->ncol > 0 && (!in->prop || (!out && !out_optional)))
     return fail(ctx, HD_EINVAL, "%s: prop and flux are required", who);
   if ((cfg->flags & HD_FLAG_PLANCK) && (!in->temf || !in->wave_lower || !in->wave_upper))
     return fail(ctx, HD_EINVAL, "%s: planck needs temf, wave_lower, wave_upper", who);
@@ -572,39 +529,30 @@ int hd_context_get_timing(const hd_context* ctx_, hd_timing* out) {
 
 int hd_context_reserve(hd_context* ctx, const hd_config* cfg, long nsolve) {
   if (!ctx || !cfg || nsolve < 0) return fail(ctx, HD_EINVAL, "hd_context_reserve: bad args");
-  if (cfg->nstr < 2 || cfg->nstr % 2 || cfg->nstr / 2 > hd::kMaxNN || cfg->nlyr < 1)
-    return fail(ctx, HD_EINVAL, "hd_context_reserve: bad config");
+  if (check_config(cfg)) return fail(ctx, HD_EINVAL, "hd_context_reserve: bad config");
   std::lock_guard<std::mutex> lk(ctx->mu);
   DeviceGuard guard;
   HD_HIP(ctx, hipSetDevice(ctx->device));
-  const bool planck_r = (cfg->flags & HD_FLAG_PLANCK) != 0;
+  const int nn = cfg->nstr / 2;
+  const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
   const long chunk = ctx->chunk > 0 ? std::min(ctx->chunk, nsolve)
-                                    : max_auto_chunk(nsolve, cfg->nstr / 2, cfg->nlyr, planck_r);
-  const size_t per = hd::scratch_doubles_per_solve(cfg->nstr / 2, cfg->nlyr,
-                                                   (cfg->flags & HD_FLAG_PLANCK) != 0);
-  // room for hd_solve_band's epilogue too, at its largest (any nwave): so a
-  // reserved context captures either solve without growing
-  const long c1 = std::max<long>(chunk, 1);
-  const int nslot_max = hd::band_slots(1);
-  const size_t band_extra = std::max(4 * (size_t)c1 + (size_t)((c1 + 63) / 64) * nslot_max *
-                                                          2 * (size_t)(cfg->nlyr + 1),
-                                     2 * (size_t)c1 * 2 * (size_t)(cfg->nlyr + 1));
-  int rc = ensure_scratch(ctx, per * c1 + band_extra);
+                                    : max_auto_chunk(nsolve, nn, cfg->nlyr, planck);
+  int rc = ensure_scratch(ctx, "hd_solve",
+                          hd::solve_reserve_doubles(nn, cfg->nlyr, planck, std::max<long>(chunk, 1)));
   if (rc) return rc;
   // and hd_solve_band's row-major route (largest call that takes it: nsolve itself)
-  if (band_rowmajor(ctx, cfg->nstr / 2, nsolve)) {
+  if (band_rowmajor(ctx, nn, nsolve)) {
     rc = ensure_pflux(ctx, (size_t)nsolve * 2 * (size_t)(cfg->nlyr + 1));
     if (rc) return rc;
   }
   rc = ensure_tables(ctx);
   if (rc) return rc;
-  return ensure_status(ctx, (size_t)nsolve);
+  int* st = nullptr;
+  return own_status(ctx, "hd_solve", (size_t)nsolve, st);
 }
 
 long hd_chunk_solves(const hd_config* cfg, long nsolve) {
-  if (!cfg || nsolve < 0 || cfg->nstr < 2 || cfg->nstr % 2 || cfg->nstr / 2 > hd::kMaxNN ||
-      cfg->nlyr < 1)
-    return -1;
+  if (!cfg || nsolve < 0 || check_config(cfg)) return -1;
   return auto_chunk(nsolve, cfg->nstr / 2, cfg->nlyr, (cfg->flags & HD_FLAG_PLANCK) != 0);
 }
 
@@ -619,67 +567,103 @@ int hd_quadrature(int nstr, double* mu, double* w) {
 
 namespace {
 
-// hd_solve's enqueue body: everything it launches ends on `stream` (the side
-// and lay streams fork from it and join back into it).
+// ---- argument builders shared by the enqueue functions ------------------------------
+
+// moments the kernels use; the delta-M rule of the prologue kernels (TaucArgs,
+// FlxLevelArgs): active when chi_nstr is among them, in prop slot 1 + nstr
+int used_moments(const hd_config* cfg) { return std::max(0, std::min(cfg->nmom, cfg->nprop - 2)); }
+
+// cmaj: column-major chunk order (hd_solve_band's fused epilogue on the register path)
+hd::PlanckArgs planck_args(const hd_config* cfg, const hd_inputs* in, double* out, long s0,
+                           int nsc, int cmaj = 0) {
+  hd::PlanckArgs pa{};
+  pa.temf = in->temf;
+  pa.btemp = in->btemp;
+  pa.ttemp = in->ttemp;
+  pa.temis = in->temis;
+  pa.wlo = in->wave_lower;
+  pa.whi = in->wave_upper;
+  pa.out = out;
+  pa.s0 = s0;
+  pa.nsc = nsc;
+  pa.ncol = in->ncol;
+  pa.nlyr = cfg->nlyr;
+  pa.cmaj = cmaj;
+  pa.nwave = in->nwave;
+  return pa;
+}
+
+hd::TaucArgs tauc_args(const hd_config* cfg, const hd_inputs* in, double* out, long s0, int nsc,
+                       int cmaj = 0) {
+  hd::TaucArgs ta{};
+  ta.prop = in->prop;
+  ta.out = out;
+  ta.s0 = s0;
+  ta.nsc = nsc;
+  ta.nlyr = cfg->nlyr;
+  ta.nprop = cfg->nprop;
+  ta.use_f = used_moments(cfg) >= cfg->nstr;
+  ta.f_slot = 1 + cfg->nstr;
+  ta.cmaj = cmaj;
+  ta.nwave = in->nwave;
+  ta.ncol = in->ncol;
+  return ta;
+}
+
+// The chunk's timing quadruple (layer start / end, sweep start / end) from the event
+// pool, or null with timing off.
+int timing_quad(hd_context* ctx, hipEvent_t** ev) {
+  *ev = nullptr;
+  if (!ctx->timing) return HD_OK;
+  if (ctx->pool_used >= 4 * 512) {
+    const int rc = resolve_timing(ctx);
+    if (rc) return rc;
+  }
+  while (ctx->pool.size() < ctx->pool_used + 4) {
+    hipEvent_t e;
+    HD_HIP(ctx, hipEventCreate(&e));
+    ctx->pool.push_back(e);
+  }
+  *ev = &ctx->pool[ctx->pool_used];
+  ctx->pool_used += 4;
+  return HD_OK;
+}
+// launch() on `st` between events i and i + 1 of the quadruple: i = 0 the layer kernel,
+// i = 2 the sweep
+template <class Launch>
+hipError_t timed(hipEvent_t* ev, int i, hipStream_t st, Launch&& launch) {
+  if (!ev) return launch();
+  const hipError_t r0 = hipEventRecord(ev[i], st);
+  const hipError_t e = launch();
+  const hipError_t r1 = hipEventRecord(ev[i + 1], st);
+  return e != hipSuccess ? e : (r0 != hipSuccess ? r0 : r1);
+}
+
+// ---- hd_solve, hd_solve_flx, hd_solve_band ------------------------------------------
+
+// One call's shared setup: what the pipelines below (one function per path) launch from.
 // flx (hd_solve_flx; flux and band null): the same chunks and streams with the flx
 // instantiations -- register path hd_layer_kernel -> hd_sweep_flx_kernel ->
 // hd_backsub_flx_kernel / _tail_kernel (never the NN-lane, LDS-state or column sweeps),
 // team path hd_team_mfma_layer_kernel -> hd_team_mfma_sweep_flx_kernel -- over the wider
 // back-substitution records, plus the per-level prologue hd_flx_level_kernel, whose
 // output only the sweep (surface level) and the back-substitution read.
-int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
-                  const hd_band* band, int*& status, hipStream_t stream, double* flx = nullptr) {
-  int rc = HD_OK;
-  const long nsolve = (long)in->nwave * in->ncol;
-  const int nn = cfg->nstr / 2;
-  const int nlyr = cfg->nlyr;
-  const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
-  const bool sync = status == nullptr;
-  const bool reg = nn <= hd::kMaxRegNN;
-  const size_t nlev2 = 2 * (size_t)(nlyr + 1);
-
-  long chunk = ctx->chunk > 0 ? std::min(ctx->chunk, nsolve) : auto_chunk(nsolve, nn, nlyr, planck);
-  const size_t ne1 = hd::layer_record_doubles(nn);
-  const size_t ne2 = flx ? hd::bsub_flx_record_doubles(nn) : hd::bsub_record_doubles(nn);
-  const int nb = 2;  // buffers of the per-chunk regions (two chunks in flight)
-  // hd_solve_flx: the wider records and the per-level terms [3][nlyr+1], per buffer
-  const size_t per = hd::scratch_doubles_per_solve(nn, nlyr, planck) +
-                     (flx ? nb * ((ne2 - hd::bsub_record_doubles(nn)) * nlyr + 3 * (size_t)(nlyr + 1))
-                          : 0);
-  // fused band epilogue: register path -- column-major chunks, the surface
-  // fluxes of two chunks in flight [2][2][chunk] and one chunk's run partials
-  // [wave][nslot][lev][2]; team path -- one chunk's fluxes when the caller
-  // keeps none
-  const int nslot = band ? hd::band_slots(in->nwave) : 0;
-  size_t band_extra = 0;
-  if (band && reg) band_extra = 4 * (size_t)chunk + (size_t)((chunk + 63) / 64) * nslot * nlev2;
-  // team path without caller fluxes: two chunk flux buffers (the band reduce of chunk
-  // k runs on the side stream beside sweep k+1)
-  if (band && !reg && !flux) band_extra = 2 * (size_t)chunk * nlev2;
-  rc = ensure_scratch(ctx, per * chunk + band_extra);
-  if (rc) return rc;
-  rc = ensure_tables(ctx);
-  if (rc) return rc;
-  if (sync) {
-    rc = ensure_status(ctx, (size_t)nsolve);
-    if (rc) return rc;
-    status = ctx->status;
-  }
-  HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
-  HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
-  const int nm = std::max(0, std::min(cfg->nmom, cfg->nprop - 2));
-  const int cmaj = band && reg ? 1 : 0;
-
-  // a register-path call of one chunk has nothing to overlap: it runs wholly on
-  // the caller's stream (prologue, layer kernel, sweep, tail back-substitution),
-  // without the fork/join of the three-stream pipeline below (C1/C3 latency)
-  // nstr 16 by the column kernel: every chunk wholly on the caller's stream
-  const bool col = reg && nn == 8 && ctx->column && !flx;
-  const bool single = reg && !col && nsolve <= chunk;
-  // team path with several chunks: chunk k+1's prologue and layer kernel on the
-  // `lay` stream beside chunk k's sweep on the caller's stream
-  const bool team_pipe = !reg && nsolve > chunk;
-  const bool beam = in->fbeam != nullptr;
+struct SolveCall {
+  hd_context* ctx;
+  const hd_config* cfg;
+  const hd_inputs* in;
+  double* flux;
+  double* flx;
+  const hd_band* band;
+  int* status;
+  hipStream_t stream;
+  const char* who;  // the entry point in the messages
+  long nsolve, chunk;
+  int nn, nlyr;
+  int nm;     // moments used
+  int cmaj;   // column-major chunk order (solve_of): the fused band epilogue, register path
+  int nslot;  // band: column slots per wave
+  bool planck, reg;
   // Without Planck emission the layer kernels' beam sources are for a unit beam at
   // the layer top and the sweep scales them by exp(-tau_c/mu0) from its own running
   // depth, so no chunk needs the cumulative-depth prologue.  Register path: it sat
@@ -689,142 +673,23 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   // 254-register waves hold (up to 3.3 ms of a 48 ms C5 step,
   // profiles/r04/c5_timeline_last_step_v2.txt).  With Planck the sources mix beam
   // and thermal terms and the prologue stays.
-  const bool beam_in_sweep = beam && !planck;
-  const bool need_tauc = beam && !beam_in_sweep;
-  const bool need_pro = planck || need_tauc;  // prologue output the layer kernel reads
-  const bool any_pro = need_pro || flx;       // ... or the sweep / back-substitution
-  // Scratch regions, sized for the largest chunk so that no region moves between
-  // chunks (inside a region the kernels interleave with the chunk's own nsc):
-  //   layer ops[nb] | bsub[nb] | xsurf[nb] | planck[nb] | tauc[nb]
-  // Register path (three streams): chunk k uses buffer k&1; its layer kernel
-  // (stream lay) runs beside chunk k-1's sweep (the caller's stream), its
-  // back-substitution (side stream) beside chunk k+1's layer kernel, and chunk
-  // k+1's tauc/planck prologue (side stream) beside chunk k.
-  double* layer_b[2];
-  double* bsub_b[2];
-  double* xsurf_b[2];
-  double* planck_b[2];
-  double* tauc_b[2];
-  double* lvl_b[2] = {nullptr, nullptr};  // hd_solve_flx: per-level terms
-  double* band_q = nullptr;  // band-epilogue scratch after the regions
-  {
-    double* q = ctx->scratch;
-    for (int b = 0; b < nb; ++b, q += ne1 * nlyr * (size_t)chunk) layer_b[b] = q;
-    for (int b = 0; b < nb; ++b, q += ne2 * nlyr * (size_t)chunk) bsub_b[b] = q;
-    for (int b = 0; b < nb; ++b, q += chunk) xsurf_b[b] = q;
-    for (int b = 0; b < nb; ++b) {
-      planck_b[b] = planck ? q : nullptr;
-      if (planck) q += (size_t)(nlyr + 3) * chunk;
-    }
-    for (int b = 0; b < nb; ++b, q += (size_t)nlyr * chunk) tauc_b[b] = q;
-    if (flx)
-      for (int b = 0; b < nb; ++b, q += 3 * (size_t)(nlyr + 1) * chunk) lvl_b[b] = q;
-    band_q = q;
-  }
-  double* fsurf_b[2] = {nullptr, nullptr};
-  double* part = nullptr;
-  double* fchunk_b[2] = {nullptr, nullptr};
-  if (band && reg) {
-    fsurf_b[0] = band_q;
-    fsurf_b[1] = band_q + 2 * (size_t)chunk;
-    part = band_q + 4 * (size_t)chunk;
-  } else if (band && !flux) {
-    fchunk_b[0] = band_q;
-    fchunk_b[1] = band_q + (size_t)chunk * nlev2;
-  }
-  auto band_args = [&](long s0, int nsc, int b) {
-    hd::BandArgs ba{};
-    ba.part = part;
-    ba.fchunk = part ? nullptr : (flux ? flux + (size_t)s0 * nlev2 : fchunk_b[b]);
-    ba.wts = band->weight;
-    ba.bflux = band->bflux;
-    ba.s0 = s0;
-    ba.nsc = nsc;
-    ba.ncol = in->ncol;
-    ba.nwave = in->nwave;
-    ba.nlev = nlyr + 1;
-    ba.nslot = nslot;
-    return ba;
-  };
-  auto prologue_args = [&](long s0, int nsc, int b, hd::TaucArgs& ta, hd::PlanckArgs& pa) {
-    ta = hd::TaucArgs{};
-    ta.prop = in->prop;
-    ta.out = tauc_b[b];
-    ta.s0 = s0;
-    ta.nsc = nsc;
-    ta.nlyr = nlyr;
-    ta.nprop = cfg->nprop;
-    ta.use_f = nm >= cfg->nstr;
-    ta.f_slot = 1 + cfg->nstr;
-    ta.cmaj = cmaj;
-    ta.nwave = in->nwave;
-    ta.ncol = in->ncol;
-    pa = hd::PlanckArgs{};
-    pa.temf = in->temf;
-    pa.btemp = in->btemp;
-    pa.ttemp = in->ttemp;
-    pa.temis = in->temis;
-    pa.wlo = in->wave_lower;
-    pa.whi = in->wave_upper;
-    pa.out = planck_b[b];
-    pa.s0 = s0;
-    pa.nsc = nsc;
-    pa.ncol = in->ncol;
-    pa.nlyr = nlyr;
-    pa.cmaj = cmaj;
-    pa.nwave = in->nwave;
-  };
+  bool beam_in_sweep, need_tauc;
+  bool need_pro;  // prologue output the layer kernel reads
+  bool any_pro;   // ... or the sweep / back-substitution
+  hd::SolvePlan plan;
 
-  // hd_solve_flx: the chunk's per-level prologue, beside its tauc / planck one
-  auto flx_level = [&](long s0, int nsc, int b, hipStream_t st) {
-    if (!flx) return hipSuccess;
-    hd::FlxLevelArgs fa{};
-    fa.prop = in->prop;
-    fa.fbeam = in->fbeam;
-    fa.umu0 = in->umu0;
-    fa.out = lvl_b[b];
-    fa.s0 = s0;
-    fa.nsc = nsc;
-    fa.nlyr = nlyr;
-    fa.nprop = cfg->nprop;
-    fa.use_f = nm >= cfg->nstr;
-    fa.f_slot = 1 + cfg->nstr;
-    return hd::launch_flx_level(fa, st);
-  };
-  if ((reg && !single && !col) || team_pipe) {
-    // fork: the side stream sees everything the caller's stream did before this
-    // call (the inputs) -- and, under stream capture, joins the graph here
-    HD_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
-    HD_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-    HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_fork, 0));
-  }
-  long k = 0;  // chunk index
-  for (long s0 = 0; s0 < nsolve; s0 += chunk, ++k) {
-    const int nsc = (int)std::min(chunk, nsolve - s0);
-    const int buf = (int)(k & 1);
-    hd::TaucArgs ta;
-    hd::PlanckArgs pa;
-    prologue_args(s0, nsc, buf, ta, pa);
-    if (team_pipe) {
-      // buffer `buf` is free once sweep k-2 (its last reader) is done
-      if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_sweep[buf], 0));
-      hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, ctx->lay);
-      HD_HIP(ctx, flx_level(s0, nsc, buf, ctx->lay));
-    } else if (!reg || single || col) {
-      hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, stream);
-      HD_HIP(ctx, flx_level(s0, nsc, buf, stream));
-    } else if (k == 0 && any_pro) {
-      hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, ctx->side);
-      HD_HIP(ctx, flx_level(s0, nsc, buf, ctx->side));
-      HD_HIP(ctx, hipEventRecord(ctx->ev_pro[0], ctx->side));
-    }
+  double* at(hd::SolveRegion r, int buf) const { return plan.at(ctx->scratch, r, buf); }
+  int nsc_at(long s0) const { return (int)std::min(chunk, nsolve - s0); }
+  long nchunk() const { return (nsolve + chunk - 1) / chunk; }
+
+  hd::LayerArgs layer_args(long s0, int nsc, int buf) const {
     hd::LayerArgs la{};
     la.prop = in->prop;
-    la.tauc = need_tauc ? tauc_b[buf] : nullptr;  // null with a beam: unit beam at the top
+    la.tauc = need_tauc ? at(hd::kRTauc, buf) : nullptr;  // null with a beam: unit beam at the top
     la.fbeam = in->fbeam;
     la.umu0 = in->umu0;
-    la.planckv = planck_b[buf];
-    la.scr = layer_b[buf];
+    la.planckv = at(hd::kRPlanck, buf);
+    la.scr = at(hd::kRLayer, buf);
     la.status = status;
     la.anyerr = ctx->anyerr;
     la.s0 = s0;
@@ -839,16 +704,19 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
     la.sink = ctx->sink;
     la.cmaj = cmaj;
     la.nwave = in->nwave;
+    return la;
+  }
+  hd::SweepArgs sweep_args(long s0, int nsc, int buf) const {
     hd::SweepArgs sa{};
-    sa.scr = layer_b[buf];
-    sa.bsub = bsub_b[buf];
-    sa.xsurf = xsurf_b[buf];
+    sa.scr = at(hd::kRLayer, buf);
+    sa.bsub = at(hd::kRBsub, buf);
+    sa.xsurf = at(hd::kRXsurf, buf);
     sa.flux = flux;
     sa.fbeam = in->fbeam;
     sa.umu0 = in->umu0;
     sa.albedo = in->albedo;
     sa.fisot = in->fisot;
-    sa.planckv = planck_b[buf];
+    sa.planckv = at(hd::kRPlanck, buf);
     sa.status = status;
     sa.anyerr = ctx->anyerr;
     sa.s0 = s0;
@@ -863,147 +731,276 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
     sa.lean = ctx->lean;
     sa.quad = ctx->quad;
     sa.lean8 = ctx->lean8;
-    hd::FlxArgs fx{};
-    fx.flx = flx;
-    fx.lvl = lvl_b[buf];
     if (band && reg) {
       sa.wts = band->weight;
-      sa.part = part;
-      sa.fsurf = fsurf_b[buf];
+      sa.part = at(hd::kRPart, 0);
+      sa.fsurf = at(hd::kRFsurf, buf);
       sa.nslot = nslot;
       sa.rsteps = hd::band_steps(in->nwave);
     } else if (band && !flux) {
-      sa.flux = fchunk_b[buf];
+      sa.flux = at(hd::kRFchunk, buf);
       sa.flux_local = 1;
     }
-    hipEvent_t* ev = nullptr;
-    if (ctx->timing) {
-      if (ctx->pool_used >= 4 * 512) {
-        rc = resolve_timing(ctx);
-        if (rc) return rc;
-      }
-      while (ctx->pool.size() < ctx->pool_used + 4) {
-        hipEvent_t e;
-        HD_HIP(ctx, hipEventCreate(&e));
-        ctx->pool.push_back(e);
-      }
-      ev = &ctx->pool[ctx->pool_used];
-      ctx->pool_used += 4;
-    }
-    hipError_t e = hipSuccess;
-    if (col) {
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], stream));
-      e = hd::launch_column_nn(nn, la, sa, stream);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], stream));
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-      if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), stream);
-    } else if (single) {
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], stream));
-      e = hd::launch_layer_nn(nn, la, stream);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], stream));
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-      if (e == hipSuccess)
-        e = flx ? hd::launch_sweep_flx_nn(nn, sa, fx, stream) : hd::launch_sweep_nn(nn, sa, stream);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-      if (e == hipSuccess)
-        e = flx ? hd::launch_backsub_flx_nn(nn, sa, fx, stream, true)
-                : hd::launch_backsub_nn(nn, sa, stream, true);
-      if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), stream);
-    } else if (reg) {
-      // layer kernel k on `lay`: its inputs (prologue k) are in, and sweep k-2,
-      // the last reader of layer records[buf], is done
-      if (need_pro) HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_pro[buf], 0));
-      if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_sweep[buf], 0));
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], ctx->lay));
-      e = hd::launch_layer_nn(nn, la, ctx->lay);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], ctx->lay));
-      HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], ctx->lay));
-      // sweep k on the caller's stream: after layer k, and after back-substitution
-      // k-2, the last reader of the back-substitution records[buf]
-      if (e == hipSuccess) {
-        HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
-        if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
-        // hd_solve_flx without a prologue the layer kernel waited for: the sweep reads it
-        if (flx && !need_pro) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_pro[buf], 0));
-        if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-        e = flx ? hd::launch_sweep_flx_nn(nn, sa, fx, stream) : hd::launch_sweep_nn(nn, sa, stream);
-        if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-      }
-    } else if (team_pipe) {
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], ctx->lay));
-      e = hd::launch_team_layer_nn(nn, la, ctx->lay);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], ctx->lay));
-      HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], ctx->lay));
-      if (e == hipSuccess) {
-        HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
-        // the chunk flux buffer[buf] is free once band reduce k-2 (its reader) is done
-        if (band && k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
-        if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-        e = flx ? hd::launch_team_sweep_flx_nn(nn, sa, fx, stream)
-                : hd::launch_team_sweep_nn(nn, sa, stream);
-        if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-      }
-      HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
-      // the band reduce of chunk k on the side stream: on the caller's stream it sat
-      // between sweep k and sweep k+1 waiting for SIMDs the co-running layer kernel
-      // held (6.4 ms average per 11 us launch, profiles/r04/c5_kernel_stats_final.csv);
-      // the reduces stay in chunk order (bflux accumulates chunk by chunk)
-      if (e == hipSuccess && band) {
-        HD_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_sweep[buf], 0));
-        e = hd::launch_band_reduce(band_args(s0, nsc, buf), ctx->side);
-        HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], ctx->side));
-      }
-    } else if (flx) {  // team path, one chunk
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[0], stream));
-      e = hd::launch_team_layer_nn(nn, la, stream);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[1], stream));
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[2], stream));
-      if (e == hipSuccess) e = hd::launch_team_sweep_flx_nn(nn, sa, fx, stream);
-      if (ev) HD_HIP(ctx, hipEventRecord(ev[3], stream));
-    } else {
-      e = hd::launch_solve_chunk_team(nn, nullptr, nullptr, la, sa, stream, ev);
-      if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), stream);
-    }
-    if (e != hipSuccess)
-      return fail(ctx, HD_EHIP, "%s: launch failed: %s", flx ? "hd_solve_flx" : "hd_solve",
-                  hipGetErrorString(e));
-    if (reg && !single && !col) {
-      HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
-      // next chunk's prologue into the other buffer (free: the side stream already
-      // waited for the sweep of chunk k-1, the last user of that buffer)
-      const long s1 = s0 + chunk;
-      if (s1 < nsolve && any_pro) {
-        hd::TaucArgs ta1;
-        hd::PlanckArgs pa1;
-        prologue_args(s1, (int)std::min(chunk, nsolve - s1), buf ^ 1, ta1, pa1);
-        hd::launch_prologue(planck ? &pa1 : nullptr, need_tauc ? &ta1 : nullptr, ctx->side);
-        HD_HIP(ctx, flx_level(s1, (int)std::min(chunk, nsolve - s1), buf ^ 1, ctx->side));
-        HD_HIP(ctx, hipEventRecord(ctx->ev_pro[buf ^ 1], ctx->side));
-      }
-      HD_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_sweep[buf], 0));
-      // The last chunk's back-substitution takes the uncapped tail kernel (nothing
-      // overlaps it).  With at most three chunks every chunk's does: the capped
-      // kernel then still runs beside the last layer kernel when the step could
-      // end, while the tail kernel takes the SIMDs briefly and is done -- 8-GPU
-      // rank shape (80 000 solves, 2 chunks) 9.47 -> 10.50 M solves/s, 4-GPU
-      // (160 000, 3 chunks) 10.0 -> 10.3 M; with 5 and 10 chunks the capped kernel
-      // hidden under the next layer kernel stays ahead (profiles/r02_tail_ab/)
-      const bool tail = s1 >= nsolve || (nsolve + chunk - 1) / chunk <= 3;
-      e = flx ? hd::launch_backsub_flx_nn(nn, sa, fx, ctx->side, tail)
-              : hd::launch_backsub_nn(nn, sa, ctx->side, tail);
-      if (e == hipSuccess && band) e = hd::launch_band_reduce(band_args(s0, nsc, buf), ctx->side);
-      if (e != hipSuccess)
-        return fail(ctx, HD_EHIP, "%s: back-substitution launch failed: %s",
-                    flx ? "hd_solve_flx" : "hd_solve", hipGetErrorString(e));
-      HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], ctx->side));
-    }
+    return sa;
   }
-  if ((reg && !single && !col) || (team_pipe && band)) {  // every chunk's fluxes complete
-    for (long b = 0; b < std::min<long>(k, 2); ++b)
+  hd::FlxArgs flx_args(int buf) const {
+    hd::FlxArgs fx{};
+    fx.flx = flx;
+    fx.lvl = at(hd::kRLvl, buf);
+    return fx;
+  }
+  hd::BandArgs band_args(long s0, int nsc, int buf) const {
+    hd::BandArgs ba{};
+    ba.part = at(hd::kRPart, 0);
+    ba.fchunk = ba.part ? nullptr
+                        : (flux ? flux + (size_t)s0 * 2 * (size_t)(nlyr + 1) : at(hd::kRFchunk, buf));
+    ba.wts = band->weight;
+    ba.bflux = band->bflux;
+    ba.s0 = s0;
+    ba.nsc = nsc;
+    ba.ncol = in->ncol;
+    ba.nwave = in->nwave;
+    ba.nlev = nlyr + 1;
+    ba.nslot = nslot;
+    return ba;
+  }
+
+  // a chunk's prologue on `st`: the tauc / planck kernels the call needs and, for
+  // hd_solve_flx, the chunk's per-level prologue beside them
+  int prologue(long s0, int nsc, int buf, hipStream_t st) const {
+    const hd::PlanckArgs pa = planck_args(cfg, in, at(hd::kRPlanck, buf), s0, nsc, cmaj);
+    const hd::TaucArgs ta = tauc_args(cfg, in, at(hd::kRTauc, buf), s0, nsc, cmaj);
+    hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, st);
+    if (!flx) return HD_OK;
+    hd::FlxLevelArgs fa{};
+    fa.prop = in->prop;
+    fa.fbeam = in->fbeam;
+    fa.umu0 = in->umu0;
+    fa.out = at(hd::kRLvl, buf);
+    fa.s0 = s0;
+    fa.nsc = nsc;
+    fa.nlyr = nlyr;
+    fa.nprop = cfg->nprop;
+    fa.use_f = ta.use_f;
+    fa.f_slot = ta.f_slot;
+    HD_HIP(ctx, hd::launch_flx_level(fa, st));
+    return HD_OK;
+  }
+  // the path's kernels
+  hipError_t layer(const hd::LayerArgs& la, hipStream_t st) const {
+    return reg ? hd::launch_layer_nn(nn, la, st) : hd::launch_team_layer_nn(nn, la, st);
+  }
+  hipError_t sweep(const hd::SweepArgs& sa, int buf, hipStream_t st) const {
+    if (reg)
+      return flx ? hd::launch_sweep_flx_nn(nn, sa, flx_args(buf), st)
+                 : hd::launch_sweep_nn(nn, sa, st);
+    return flx ? hd::launch_team_sweep_flx_nn(nn, sa, flx_args(buf), st)
+               : hd::launch_team_sweep_nn(nn, sa, st);
+  }
+  hipError_t backsub(const hd::SweepArgs& sa, int buf, hipStream_t st, bool tail) const {
+    return flx ? hd::launch_backsub_flx_nn(nn, sa, flx_args(buf), st, tail)
+               : hd::launch_backsub_nn(nn, sa, st, tail);
+  }
+  int launch_failed(hipError_t e, const char* what = "launch") const {
+    return fail(ctx, HD_EHIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+  }
+  // fork: the side stream sees everything the caller's stream did before this
+  // call (the inputs) -- and, under stream capture, joins the graph here
+  int fork() const {
+    HD_HIP(ctx, hipEventRecord(ctx->ev_fork, stream));
+    HD_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    HD_HIP(ctx, hipStreamWaitEvent(ctx->lay, ctx->ev_fork, 0));
+    return HD_OK;
+  }
+  // join: every chunk's fluxes complete (the last work on `side` of each buffer)
+  int join() const {
+    for (long b = 0; b < std::min<long>(nchunk(), 2); ++b)
       HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[b], 0));
+    return HD_OK;
+  }
+};
+
+// A call of one chunk, on either path, has nothing to overlap: it runs wholly on the
+// caller's stream (prologue, layer kernel, sweep and, on the register path, the tail
+// back-substitution), without the fork/join of the pipelines below (C1/C3 latency).
+int solve_one_chunk(const SolveCall& c) {
+  const int nsc = (int)c.nsolve;
+  int rc = c.prologue(0, nsc, 0, c.stream);
+  if (rc) return rc;
+  const hd::LayerArgs la = c.layer_args(0, nsc, 0);
+  const hd::SweepArgs sa = c.sweep_args(0, nsc, 0);
+  hipEvent_t* ev;
+  rc = timing_quad(c.ctx, &ev);
+  if (rc) return rc;
+  hipError_t e = timed(ev, 0, c.stream, [&] { return c.layer(la, c.stream); });
+  if (e == hipSuccess) e = timed(ev, 2, c.stream, [&] { return c.sweep(sa, 0, c.stream); });
+  if (e == hipSuccess && c.reg) e = c.backsub(sa, 0, c.stream, true);
+  if (e == hipSuccess && c.band) e = hd::launch_band_reduce(c.band_args(0, nsc, 0), c.stream);
+  return e == hipSuccess ? HD_OK : c.launch_failed(e);
+}
+
+// nstr 16 by the column kernel (A/B build): every chunk wholly on the caller's stream
+int solve_column(const SolveCall& c) {
+  long k = 0;
+  for (long s0 = 0; s0 < c.nsolve; s0 += c.chunk, ++k) {
+    const int nsc = c.nsc_at(s0), buf = (int)(k & 1);
+    int rc = c.prologue(s0, nsc, buf, c.stream);
+    if (rc) return rc;
+    const hd::LayerArgs la = c.layer_args(s0, nsc, buf);
+    const hd::SweepArgs sa = c.sweep_args(s0, nsc, buf);
+    hipEvent_t* ev;
+    rc = timing_quad(c.ctx, &ev);
+    if (rc) return rc;
+    hipError_t e =
+        timed(ev, 0, c.stream, [&] { return hd::launch_column_nn(c.nn, la, sa, c.stream); });
+    if (e == hipSuccess) e = timed(ev, 2, c.stream, [] { return hipSuccess; });
+    if (e == hipSuccess && c.band) e = hd::launch_band_reduce(c.band_args(s0, nsc, buf), c.stream);
+    if (e != hipSuccess) return c.launch_failed(e);
   }
   return HD_OK;
+}
+
+// Register path (three streams): chunk k uses buffer k&1; its layer kernel
+// (stream lay) runs beside chunk k-1's sweep (the caller's stream), its
+// back-substitution (side stream) beside chunk k+1's layer kernel, and chunk
+// k+1's tauc/planck prologue (side stream) beside chunk k.
+int solve_reg_pipeline(const SolveCall& c) {
+  hd_context* ctx = c.ctx;
+  hipStream_t stream = c.stream, lay = ctx->lay, side = ctx->side;
+  int rc = c.fork();
+  if (rc) return rc;
+  if (c.any_pro) {  // the first chunk's prologue
+    rc = c.prologue(0, c.nsc_at(0), 0, side);
+    if (rc) return rc;
+    HD_HIP(ctx, hipEventRecord(ctx->ev_pro[0], side));
+  }
+  long k = 0;
+  for (long s0 = 0; s0 < c.nsolve; s0 += c.chunk, ++k) {
+    const int nsc = c.nsc_at(s0), buf = (int)(k & 1);
+    const hd::LayerArgs la = c.layer_args(s0, nsc, buf);
+    const hd::SweepArgs sa = c.sweep_args(s0, nsc, buf);
+    hipEvent_t* ev;
+    rc = timing_quad(ctx, &ev);
+    if (rc) return rc;
+    // layer kernel k on `lay`: its inputs (prologue k) are in, and sweep k-2,
+    // the last reader of layer records[buf], is done
+    if (c.need_pro) HD_HIP(ctx, hipStreamWaitEvent(lay, ctx->ev_pro[buf], 0));
+    if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(lay, ctx->ev_sweep[buf], 0));
+    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, lay); });
+    HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], lay));
+    if (e != hipSuccess) return c.launch_failed(e);
+    // sweep k on the caller's stream: after layer k, and after back-substitution
+    // k-2, the last reader of the back-substitution records[buf]
+    HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
+    if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
+    // hd_solve_flx without a prologue the layer kernel waited for: the sweep reads it
+    if (c.flx && !c.need_pro) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_pro[buf], 0));
+    e = timed(ev, 2, stream, [&] { return c.sweep(sa, buf, stream); });
+    if (e != hipSuccess) return c.launch_failed(e);
+    HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
+    // next chunk's prologue into the other buffer (free: the side stream already
+    // waited for the sweep of chunk k-1, the last user of that buffer)
+    const long s1 = s0 + c.chunk;
+    if (s1 < c.nsolve && c.any_pro) {
+      rc = c.prologue(s1, c.nsc_at(s1), buf ^ 1, side);
+      if (rc) return rc;
+      HD_HIP(ctx, hipEventRecord(ctx->ev_pro[buf ^ 1], side));
+    }
+    HD_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_sweep[buf], 0));
+    // The last chunk's back-substitution takes the uncapped tail kernel (nothing
+    // overlaps it).  With at most three chunks every chunk's does: the capped
+    // kernel then still runs beside the last layer kernel when the step could
+    // end, while the tail kernel takes the SIMDs briefly and is done -- 8-GPU
+    // rank shape (80 000 solves, 2 chunks) 9.47 -> 10.50 M solves/s, 4-GPU
+    // (160 000, 3 chunks) 10.0 -> 10.3 M; with 5 and 10 chunks the capped kernel
+    // hidden under the next layer kernel stays ahead (profiles/r02_tail_ab/)
+    const bool tail = s1 >= c.nsolve || c.nchunk() <= 3;
+    e = c.backsub(sa, buf, side, tail);
+    if (e == hipSuccess && c.band) e = hd::launch_band_reduce(c.band_args(s0, nsc, buf), side);
+    if (e != hipSuccess) return c.launch_failed(e, "back-substitution launch");
+    HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], side));
+  }
+  return c.join();
+}
+
+// Team path with several chunks: chunk k+1's prologue and layer kernel on the
+// `lay` stream beside chunk k's sweep on the caller's stream.
+int solve_team_pipeline(const SolveCall& c) {
+  hd_context* ctx = c.ctx;
+  hipStream_t stream = c.stream, lay = ctx->lay, side = ctx->side;
+  int rc = c.fork();
+  if (rc) return rc;
+  long k = 0;
+  for (long s0 = 0; s0 < c.nsolve; s0 += c.chunk, ++k) {
+    const int nsc = c.nsc_at(s0), buf = (int)(k & 1);
+    // buffer `buf` is free once sweep k-2 (its last reader) is done
+    if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(lay, ctx->ev_sweep[buf], 0));
+    rc = c.prologue(s0, nsc, buf, lay);
+    if (rc) return rc;
+    const hd::LayerArgs la = c.layer_args(s0, nsc, buf);
+    const hd::SweepArgs sa = c.sweep_args(s0, nsc, buf);
+    hipEvent_t* ev;
+    rc = timing_quad(ctx, &ev);
+    if (rc) return rc;
+    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, lay); });
+    HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], lay));
+    if (e != hipSuccess) return c.launch_failed(e);
+    HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
+    // the chunk flux buffer[buf] is free once band reduce k-2 (its reader) is done
+    if (c.band && k >= 2) HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_back[buf], 0));
+    e = timed(ev, 2, stream, [&] { return c.sweep(sa, buf, stream); });
+    HD_HIP(ctx, hipEventRecord(ctx->ev_sweep[buf], stream));
+    // the band reduce of chunk k on the side stream: on the caller's stream it sat
+    // between sweep k and sweep k+1 waiting for SIMDs the co-running layer kernel
+    // held (6.4 ms average per 11 us launch, profiles/r04/c5_kernel_stats_final.csv);
+    // the reduces stay in chunk order (bflux accumulates chunk by chunk)
+    if (e == hipSuccess && c.band) {
+      HD_HIP(ctx, hipStreamWaitEvent(side, ctx->ev_sweep[buf], 0));
+      e = hd::launch_band_reduce(c.band_args(s0, nsc, buf), side);
+      HD_HIP(ctx, hipEventRecord(ctx->ev_back[buf], side));
+    }
+    if (e != hipSuccess) return c.launch_failed(e);
+  }
+  return c.band ? c.join() : HD_OK;
+}
+
+// hd_solve's enqueue body: everything it launches ends on `stream` (the side
+// and lay streams fork from it and join back into it).  flux / flx / band: hd_solve,
+// hd_solve_flx (flx alone) and hd_solve_band (band, flux optional).
+int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
+                  double* flx, const hd_band* band, int*& status, hipStream_t stream) {
+  const long nsolve = (long)in->nwave * in->ncol;
+  const int nn = cfg->nstr / 2;
+  const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
+  const bool reg = nn <= hd::kMaxRegNN;
+  const bool beam = in->fbeam != nullptr;
+  const long chunk =
+      ctx->chunk > 0 ? std::min(ctx->chunk, nsolve) : auto_chunk(nsolve, nn, cfg->nlyr, planck);
+  const bool beam_in_sweep = beam && !planck;
+  const bool need_tauc = beam && !beam_in_sweep;
+  const bool need_pro = planck || need_tauc;
+  const bool any_pro = need_pro || flx;
+  SolveCall c{ctx, cfg, in, flux, flx, band, status, stream,
+              /*who=*/flx ? "hd_solve_flx" : "hd_solve",
+              nsolve, chunk, nn, cfg->nlyr,
+              /*nm=*/used_moments(cfg),
+              /*cmaj=*/band && reg ? 1 : 0,
+              /*nslot=*/band ? hd::band_slots(in->nwave) : 0,
+              planck, reg, beam_in_sweep, need_tauc, need_pro, any_pro,
+              hd::SolvePlan(nn, cfg->nlyr, planck, flx != nullptr,
+                            hd::band_scratch(nn, band != nullptr, flux != nullptr), in->nwave,
+                            chunk)};
+  int rc = ensure_scratch(ctx, c.who, c.plan.total);
+  if (rc) return rc;
+  rc = ensure_tables(ctx);
+  if (rc) return rc;
+  if (!status && (rc = own_status(ctx, c.who, (size_t)nsolve, status))) return rc;
+  c.status = status;
+  HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
+  HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
+  if (reg && nn == 8 && ctx->column && !flx) return solve_column(c);
+  if (nsolve <= chunk) return solve_one_chunk(c);
+  return reg ? solve_reg_pipeline(c) : solve_team_pipeline(c);
 }
 
 // The common frame of the two solve entry points: context lock, device guard,
@@ -1039,62 +1036,72 @@ int run_solve(hd_context* ctx, int* status, void* stream_, const char* what, Enq
   return HD_OK;
 }
 
+// The frame of every device-array solve entry point: null context, the context lock,
+// the argument checks (check(): the entry point's own, then validate, in the entry
+// point's order), nothing to do for an empty call, run_solve.
+template <class Check, class Enqueue>
+int solve_entry(hd_context* ctx, const char* who, const hd_inputs* in, int* status, void* stream,
+                Check&& check, Enqueue&& enqueue) {
+  if (!ctx) return fail(nullptr, HD_EINVAL, "%s: null context", who);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const int rc = check();
+  if (rc) return rc;
+  if ((long)in->nwave * in->ncol == 0) return HD_OK;
+  return run_solve(ctx, status, stream, who, enqueue);
+}
+
 }  // namespace
 
 extern "C" {
 
 int hd_solve(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
              int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = validate(ctx, cfg, in, flux);
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_solve", [&](int*& st, hipStream_t s) {
-    return solve_enqueue(ctx, cfg, in, flux, nullptr, st, s);
-  });
+  return solve_entry(
+      ctx, "hd_solve", in, status, stream, [&] { return validate(ctx, cfg, in, flux); },
+      [&](int*& st, hipStream_t s) {
+        return solve_enqueue(ctx, cfg, in, flux, nullptr, nullptr, st, s);
+      });
 }
 
 int hd_solve_flx(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flx,
                  int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_flx: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = validate(ctx, cfg, in, flx, "hd_solve_flx");
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  if (reinterpret_cast<uintptr_t>(flx) % 16)
-    return fail(ctx, HD_EINVAL, "hd_solve_flx: flx must be 16-byte aligned");
-  return run_solve(ctx, status, stream, "hd_solve_flx", [&](int*& st, hipStream_t s) {
-    return solve_enqueue(ctx, cfg, in, nullptr, nullptr, st, s, flx);
-  });
+  return solve_entry(
+      ctx, "hd_solve_flx", in, status, stream,
+      [&] {
+        const int rc = validate(ctx, cfg, in, flx, "hd_solve_flx");
+        if (rc || (long)in->nwave * in->ncol == 0) return rc;
+        if (reinterpret_cast<uintptr_t>(flx) % 16)
+          return fail(ctx, HD_EINVAL, "hd_solve_flx: flx must be 16-byte aligned");
+        return HD_OK;
+      },
+      [&](int*& st, hipStream_t s) {
+        return solve_enqueue(ctx, cfg, in, nullptr, flx, nullptr, st, s);
+      });
 }
 
 int hd_solve_band(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                   const hd_band* band, double* flux, int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_band: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!band || !band->weight || !band->bflux)
-    return fail(ctx, HD_EINVAL, "hd_solve_band: band weights and bflux are required");
-  // flux is optional here: validate against a non-null stand-in
-  int rc = validate(ctx, cfg, in, flux ? flux : band->bflux);
-  if (rc) return rc;
-  const long nsolve = (long)in->nwave * in->ncol;
-  if (nsolve == 0) return HD_OK;
-  if (!flux && band_rowmajor(ctx, cfg->nstr / 2, nsolve)) {
-    return run_solve(ctx, status, stream, "hd_solve_band", [&](int*& st, hipStream_t s) {
-      int r = ensure_pflux(ctx, (size_t)nsolve * 2 * (size_t)(cfg->nlyr + 1));
-      if (r) return r;
-      r = solve_enqueue(ctx, cfg, in, ctx->pflux, nullptr, st, s);
-      if (r) return r;
-      r = hd_band_flux(ctx->pflux, band->weight, in->nwave, in->ncol, cfg->nlyr + 1,
-                       band->bflux, s);
-      return r ? fail(ctx, r, "hd_solve_band: hd_band_flux launch failed") : HD_OK;
-    });
-  }
-  return run_solve(ctx, status, stream, "hd_solve_band", [&](int*& st, hipStream_t s) {
-    return solve_enqueue(ctx, cfg, in, flux, band, st, s);
-  });
+  return solve_entry(
+      ctx, "hd_solve_band", in, status, stream,
+      [&] {
+        if (!band || !band->weight || !band->bflux)
+          return fail(ctx, HD_EINVAL, "hd_solve_band: band weights and bflux are required");
+        return validate(ctx, cfg, in, flux, "hd_solve", /*out_optional=*/true);
+      },
+      [&](int*& st, hipStream_t s) {
+        const long nsolve = (long)in->nwave * in->ncol;
+        if (flux || !band_rowmajor(ctx, cfg->nstr / 2, nsolve))
+          return solve_enqueue(ctx, cfg, in, flux, nullptr, band, st, s);
+        int r = ensure_pflux(ctx, (size_t)nsolve * 2 * (size_t)(cfg->nlyr + 1));
+        if (r) return r;
+        r = solve_enqueue(ctx, cfg, in, ctx->pflux, nullptr, nullptr, st, s);
+        if (r) return r;
+        r = hd_band_flux(ctx->pflux, band->weight, in->nwave, in->ncol, cfg->nlyr + 1,
+                         band->bflux, s);
+        return r ? fail(ctx, r, "hd_solve_band: hd_band_flux launch failed") : HD_OK;
+      });
 }
+
 
 }  // extern "C"
 
@@ -1111,7 +1118,7 @@ int solve_host(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, doubl
   if (!cfg || !in) return fail(ctx, HD_EINVAL, "%s: null config or inputs", what);
   const bool band = bflux != nullptr;
   if (band && !weight) return fail(ctx, HD_EINVAL, "%s: band weights are required", what);
-  int rc = validate(ctx, cfg, in, flux ? flux : bflux);
+  int rc = validate(ctx, cfg, in, flux, "hd_solve", /*out_optional=*/true);  // flux or bflux is given
   if (rc) return rc;
   const long nsolve = (long)in->nwave * in->ncol;
   if (nsolve == 0) return HD_OK;
@@ -1149,18 +1156,8 @@ int solve_host(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, doubl
     if (!ctx->hev_done[b])
       HD_HIP(ctx, hipEventCreateWithFlags(&ctx->hev_done[b], hipEventDisableTiming));
   }
-  if (ctx->hstage_len < total) {
-    drain(ctx);
-    if (ctx->hstage) (void)hipFree(ctx->hstage);
-    ctx->hstage = nullptr;
-    ctx->hstage_len = 0;
-    if (hipMalloc(&ctx->hstage, total * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(ctx, HD_ENOMEM, "%s: cannot allocate %zu bytes of staging", what,
-                  total * sizeof(double));
-    }
-    ctx->hstage_len = total;
-  }
+  rc = ensure(ctx, what, kStageText, ctx->hstage, ctx->hstage_len, total);
+  if (rc) return rc;
   // uploads, solves, downloads: the per-point fluxes of piece j go back on their own
   // stream while piece j+2's arrays go up (both PCIe directions at once)
   hipStream_t cs = ctx->hstream, xs = ctx->hstream2, ds = ctx->hstream3;
@@ -1244,9 +1241,9 @@ int solve_host(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, doubl
     HD_HIP(ctx, hipStreamWaitEvent(xs, ctx->hev_in[b], 0));
     double* fd = flux ? flux_d + o * nlev2 : nullptr;
     rc = run_solve(ctx, st_d + o, xs, what, [&](int*& st, hipStream_t ss) {
-      if (!band) return solve_enqueue(ctx, cfg, &din, fd, nullptr, st, ss);
+      if (!band) return solve_enqueue(ctx, cfg, &din, fd, nullptr, nullptr, st, ss);
       hd_band bb{w_d + w0, part_d + (size_t)j * ncol * nlev2};
-      return solve_enqueue(ctx, cfg, &din, fd, &bb, st, ss);
+      return solve_enqueue(ctx, cfg, &din, fd, nullptr, &bb, st, ss);
     });
     if (rc) return rc;
     HD_HIP(ctx, hipEventRecord(ctx->hev_done[b], xs));
@@ -1296,7 +1293,7 @@ namespace {
 int validate_rad(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                  const hd_radiance* rad, double* flux, double* uu, bool rays = false) {
   const char* who = rays ? "hd_solve_rays" : "hd_solve_radiance";
-  int rc = validate(ctx, cfg, in, flux, who);
+  int rc = validate(ctx, cfg, in, flux, who, /*out_optional=*/rays);  // rays: rad or brad is given
   if (rc) return rc;
   if (!rad) return fail(ctx, HD_EINVAL, "%s: null radiance config", who);
   const int nn = cfg->nstr / 2;
@@ -1347,9 +1344,8 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   const long nsolve = (long)in->nwave * in->ncol;
   const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
   const bool beam = in->fbeam != nullptr;
-  const bool sync = status == nullptr;
   const int nm_mode = (radiances && beam) ? cfg->nstr : 1;
-  const int nmom = std::max(0, std::min(cfg->nmom, cfg->nprop - 2));
+  const int nmom = used_moments(cfg);
 
   // the user grid is copied from host arrays and its buffer may grow: a radiance
   // solve is not capturable (a replay would reread host memory the caller may have
@@ -1363,14 +1359,8 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   // replaced (launch_ray_cosines) | utau, the azimuths read from the caller's array
   const size_t ncos = rays ? (size_t)(rays->per_column ? in->ncol : 1) * numu : (size_t)numu;
   const size_t ngrid = rays ? ncos + rad->ntau : (size_t)numu + nphi + rad->ntau;
-  if (ngrid > ctx->rad_grid_len) {
-    drain(ctx);
-    if (ctx->rad_grid) (void)hipFree(ctx->rad_grid);
-    ctx->rad_grid = nullptr;
-    ctx->rad_grid_len = 0;
-    HD_HIP(ctx, hipMalloc(&ctx->rad_grid, ngrid * sizeof(double)));
-    ctx->rad_grid_len = ngrid;
-  }
+  rc = ensure(ctx, who, kGridText, ctx->rad_grid, ctx->rad_grid_len, ngrid);
+  if (rc) return rc;
   double* d_umu = ctx->rad_grid;
   double* d_phi = d_umu + numu;
   double* d_utau = rays ? d_umu + ncos : d_phi + nphi;
@@ -1383,62 +1373,25 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   if (rad->ntau)
     HD_HIP(ctx, hipMemcpyAsync(d_utau, rad->utau, rad->ntau * sizeof(double), hipMemcpyHostToDevice, stream));
 
-  // chunk: scratch per solve = modes x (per-unit records + radiance per mode) + prologue
-  const size_t per_unit = hd::rad_scratch_doubles_per_unit(nn, nlyr) + (size_t)ntau * numu;
-  const size_t per_solve = (size_t)nm_mode * per_unit + (size_t)(nlyr + 1) + nlyr +
-                           (planck ? (size_t)nlyr + 3 : 0);
-  // 16 GB of the 288 GB: chunks of ~1e5 units keep every SIMD busy in the per-unit sweep
-  const double budget = 16.0 * 1024.0 * 1024.0 * 1024.0 / 8.0;  // doubles
-  long chunk = std::max<long>(1, std::min<long>(nsolve, (long)(budget / (double)per_solve)));
-  chunk = std::min<long>(chunk, 0x7fffffffL / std::max(1, nm_mode));
-  if (ctx->chunk > 0) chunk = std::min(chunk, ctx->chunk);
-  rc = ensure_scratch(ctx, per_solve * chunk);
+  // the intensity kernels keep the register-path layer record layout at every
+  // nstr (hd::layer_record_doubles gives the team layout above nstr 16)
+  const hd::RadPlan plan(nn, nlyr, planck, nm_mode, ntau, numu, hd::rad_layer_record_doubles(nn),
+                         hd::rad_rec_doubles(nn), hd::rad_bsub_doubles(nn), nsolve, ctx->chunk);
+  rc = ensure_scratch(ctx, who, plan.total);
   if (rc) return rc;
-  if (sync) {
-    rc = ensure_status(ctx, (size_t)nsolve);
-    if (rc) return rc;
-    status = ctx->status;
-  }
+  if (!status && (rc = own_status(ctx, who, (size_t)nsolve, status))) return rc;
   HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
   HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
 
-  const size_t nuc = (size_t)nm_mode * chunk;  // units of the largest chunk
-  double* q = ctx->scratch;
-  // the intensity kernels keep the register-path layer record layout at every
-  // nstr (hd::layer_record_doubles gives the team layout above nstr 16)
-  double* r_sw = q;   q += (size_t)nlyr * hd::rad_layer_record_doubles(nn) * nuc;
-  double* r_rd = q;   q += (size_t)nlyr * hd::rad_rec_doubles(nn) * nuc;
-  double* r_bs = q;   q += (size_t)nlyr * hd::rad_bsub_doubles(nn) * nuc;
-  double* r_lev = q;  q += (size_t)(nlyr + 1) * 2 * nn * nuc;
-  double* r_cst = q;  q += (size_t)nlyr * 2 * nn * nuc;
-  double* r_radm = q; q += (size_t)ntau * numu * nuc;
-  double* r_taus = q; q += (size_t)(nlyr + 1) * chunk;
-  double* r_tauc = q; q += (size_t)nlyr * chunk;
-  double* r_planck = planck ? q : nullptr;
+  double* const q = ctx->scratch;
+  double *r_sw = q + plan.sw, *r_rd = q + plan.rd, *r_bs = q + plan.bs, *r_lev = q + plan.lev,
+         *r_cst = q + plan.cst, *r_radm = q + plan.radm, *r_taus = q + plan.taus,
+         *r_tauc = q + plan.tauc, *r_planck = planck ? q + plan.planck : nullptr;
 
-  for (long s0 = 0; s0 < nsolve; s0 += chunk) {
-    const int ns = (int)std::min(chunk, nsolve - s0);
-    hd::TaucArgs ta{};
-    ta.prop = in->prop;
-    ta.out = r_tauc;
-    ta.s0 = s0;
-    ta.nsc = ns;
-    ta.nlyr = nlyr;
-    ta.nprop = cfg->nprop;
-    ta.use_f = nmom >= cfg->nstr;
-    ta.f_slot = 1 + cfg->nstr;
-    hd::PlanckArgs pa{};
-    pa.temf = in->temf;
-    pa.btemp = in->btemp;
-    pa.ttemp = in->ttemp;
-    pa.temis = in->temis;
-    pa.wlo = in->wave_lower;
-    pa.whi = in->wave_upper;
-    pa.out = r_planck;
-    pa.s0 = s0;
-    pa.nsc = ns;
-    pa.ncol = in->ncol;
-    pa.nlyr = nlyr;
+  for (long s0 = 0; s0 < nsolve; s0 += plan.chunk) {
+    const int ns = (int)std::min(plan.chunk, nsolve - s0);
+    const hd::TaucArgs ta = tauc_args(cfg, in, r_tauc, s0, ns);
+    const hd::PlanckArgs pa = planck_args(cfg, in, r_planck, s0, ns);
     hd::launch_prologue(planck ? &pa : nullptr, beam ? &ta : nullptr, stream);
     hd::RadArgs a{};
     a.prop = in->prop;
@@ -1499,46 +1452,44 @@ extern "C" {
 int hd_solve_radiance(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                       const hd_radiance* rad, double* flux, double* uu, int* status,
                       void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_radiance: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = validate_rad(ctx, cfg, in, rad, flux, uu);
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_solve_radiance", [&](int*& st, hipStream_t s) {
-    return rad_enqueue(ctx, cfg, in, rad, nullptr, flux, uu, st, s);
-  });
+  return solve_entry(
+      ctx, "hd_solve_radiance", in, status, stream,
+      [&] { return validate_rad(ctx, cfg, in, rad, flux, uu); },
+      [&](int*& st, hipStream_t s) {
+        return rad_enqueue(ctx, cfg, in, rad, nullptr, flux, uu, st, s);
+      });
 }
 
 int hd_solve_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                   const hd_rays* rays, double* flux, double* rad, int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_solve_rays: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!rays) return fail(ctx, HD_EINVAL, "hd_solve_rays: null ray config");
-  if (!rad && !rays->brad)
-    return fail(ctx, HD_EINVAL, "hd_solve_rays: rad and brad both NULL: nothing to compute");
-  if (rays->brad && !rays->weight)
-    return fail(ctx, HD_EINVAL, "hd_solve_rays: brad needs weight");
-  if (rays->nray < 1 || !rays->umu || !rays->phi)
-    return fail(ctx, HD_EINVAL, "hd_solve_rays: rays need nray >= 1, umu and phi");
-  if (rays->per_column != 0 && rays->per_column != 1)
-    return fail(ctx, HD_EINVAL, "hd_solve_rays: per_column=%d must be 0 or 1", rays->per_column);
-  // the rest as hd_solve_radiance (nstr, ntau/utau, corint); the cosines are device
-  // data, checked by the kernels.  flux is optional: validate against a stand-in
-  hd_radiance view{};
-  view.ntau = rays->ntau;
-  view.utau = rays->utau;
-  view.numu = rays->nray;
-  view.nphi = 1;
-  view.phi0 = rays->phi0;
-  view.onlyfl = 0;
-  view.corint = rays->corint;
-  double* out = rad ? rad : rays->brad;
-  int rc = validate_rad(ctx, cfg, in, &view, flux ? flux : out, out, /*rays=*/true);
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_solve_rays", [&](int*& st, hipStream_t s) {
-    return rad_enqueue(ctx, cfg, in, &view, rays, flux, rad, st, s);
-  });
+  hd_radiance view{};  // the rays as hd_solve_radiance's user grid
+  return solve_entry(
+      ctx, "hd_solve_rays", in, status, stream,
+      [&] {
+        if (!rays) return fail(ctx, HD_EINVAL, "hd_solve_rays: null ray config");
+        if (!rad && !rays->brad)
+          return fail(ctx, HD_EINVAL, "hd_solve_rays: rad and brad both NULL: nothing to compute");
+        if (rays->brad && !rays->weight)
+          return fail(ctx, HD_EINVAL, "hd_solve_rays: brad needs weight");
+        if (rays->nray < 1 || !rays->umu || !rays->phi)
+          return fail(ctx, HD_EINVAL, "hd_solve_rays: rays need nray >= 1, umu and phi");
+        if (rays->per_column != 0 && rays->per_column != 1)
+          return fail(ctx, HD_EINVAL, "hd_solve_rays: per_column=%d must be 0 or 1",
+                      rays->per_column);
+        // the rest as hd_solve_radiance (nstr, ntau/utau, corint); the cosines are device
+        // data, checked by the kernels
+        view.ntau = rays->ntau;
+        view.utau = rays->utau;
+        view.numu = rays->nray;
+        view.nphi = 1;
+        view.phi0 = rays->phi0;
+        view.onlyfl = 0;
+        view.corint = rays->corint;
+        return validate_rad(ctx, cfg, in, &view, flux, rad ? rad : rays->brad, /*rays=*/true);
+      },
+      [&](int*& st, hipStream_t s) {
+        return rad_enqueue(ctx, cfg, in, &view, rays, flux, rad, st, s);
+      });
 }
 
 }  // extern "C"
@@ -1547,8 +1498,6 @@ int hd_solve_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
 // Beer-Lambert solver (include/hdbeer.h; kernels in hd_beer.hip)
 // ============================================================================
 namespace {
-
-constexpr long kBeerChunk = 262144;  // solves per automatic chunk
 
 // flux given / band given: hd_beer_flux(_band); rays given: hd_beer_rays (out = rad)
 int beer_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* out,
@@ -1559,45 +1508,24 @@ int beer_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, dou
   const int nn = cfg->nstr / 2;
   const int nlyr = cfg->nlyr;
   const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
-  const bool sync = status == nullptr;
   const size_t m = rays ? (size_t)rays->nray : 2 * (size_t)(nlyr + 1);  // values per solve
   const double* weight = rays ? rays->weight : (band ? band->weight : nullptr);
   double* bout = rays ? rays->brad : (band ? band->bflux : nullptr);
-  const long chunk = std::min(nsolve, ctx->chunk > 0 ? ctx->chunk : kBeerChunk);
-  // scratch of one chunk: planck [nlyr+3] | xsurf (rays) | per-wave values (band sum
-  // without a caller buffer for them)
-  const size_t n_planck = planck ? (size_t)(nlyr + 3) * chunk : 0;
-  const size_t n_xsurf = rays ? (size_t)chunk : 0;
-  const size_t n_local = out ? 0 : m * (size_t)chunk;
-  rc = ensure_scratch(ctx, std::max<size_t>(n_planck + n_xsurf + n_local, 1));
+  const hd::BeerPlan plan(nlyr, planck, rays != nullptr, out != nullptr, m, nsolve, ctx->chunk);
+  rc = ensure_scratch(ctx, who, plan.total);
   if (rc) return rc;
-  if (sync) {
-    rc = ensure_status(ctx, (size_t)nsolve);
-    if (rc) return rc;
-    status = ctx->status;
-  }
+  if (!status && (rc = own_status(ctx, who, (size_t)nsolve, status))) return rc;
   HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
   HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
   if (bout) HD_HIP(ctx, hipMemsetAsync(bout, 0, sizeof(double) * in->ncol * m, stream));
-  double* planck_q = planck ? ctx->scratch : nullptr;
-  double* xsurf_q = ctx->scratch + n_planck;
-  double* local_q = ctx->scratch + n_planck + n_xsurf;
+  double* planck_q = planck ? ctx->scratch + plan.planck : nullptr;
+  double* xsurf_q = ctx->scratch + plan.xsurf;
+  double* local_q = ctx->scratch + plan.local;
   const hd::QuadHost& q = quad_host()[nn - 1];
-  for (long s0 = 0; s0 < nsolve; s0 += chunk) {
-    const int nsc = (int)std::min(chunk, nsolve - s0);
+  for (long s0 = 0; s0 < nsolve; s0 += plan.chunk) {
+    const int nsc = (int)std::min(plan.chunk, nsolve - s0);
     if (planck) {
-      hd::PlanckArgs pa{};
-      pa.temf = in->temf;
-      pa.btemp = in->btemp;
-      pa.ttemp = in->ttemp;
-      pa.temis = in->temis;
-      pa.wlo = in->wave_lower;
-      pa.whi = in->wave_upper;
-      pa.out = planck_q;
-      pa.s0 = s0;
-      pa.nsc = nsc;
-      pa.ncol = in->ncol;
-      pa.nlyr = nlyr;
+      const hd::PlanckArgs pa = planck_args(cfg, in, planck_q, s0, nsc);
       hd::launch_prologue(&pa, nullptr, stream);
     }
     double* vals = out ? out + (size_t)s0 * m : local_q;  // the chunk's per-wave values
@@ -1661,50 +1589,51 @@ extern "C" {
 
 int hd_beer_flux(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
                  int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_flux: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  int rc = validate(ctx, cfg, in, flux, "hd_beer_flux");
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_beer_flux", [&](int*& st, hipStream_t s) {
-    return beer_enqueue(ctx, cfg, in, flux, nullptr, nullptr, st, s, "hd_beer_flux");
-  });
+  return solve_entry(
+      ctx, "hd_beer_flux", in, status, stream,
+      [&] { return validate(ctx, cfg, in, flux, "hd_beer_flux"); },
+      [&](int*& st, hipStream_t s) {
+        return beer_enqueue(ctx, cfg, in, flux, nullptr, nullptr, st, s, "hd_beer_flux");
+      });
 }
 
 int hd_beer_flux_band(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                       const hd_band* band, double* flux, int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_flux_band: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!band || !band->weight || !band->bflux)
-    return fail(ctx, HD_EINVAL, "hd_beer_flux_band: band weights and bflux are required");
-  int rc = validate(ctx, cfg, in, flux ? flux : band->bflux, "hd_beer_flux_band");
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_beer_flux_band", [&](int*& st, hipStream_t s) {
-    return beer_enqueue(ctx, cfg, in, flux, band, nullptr, st, s, "hd_beer_flux_band");
-  });
+  return solve_entry(
+      ctx, "hd_beer_flux_band", in, status, stream,
+      [&] {
+        if (!band || !band->weight || !band->bflux)
+          return fail(ctx, HD_EINVAL, "hd_beer_flux_band: band weights and bflux are required");
+        return validate(ctx, cfg, in, flux, "hd_beer_flux_band", /*out_optional=*/true);
+      },
+      [&](int*& st, hipStream_t s) {
+        return beer_enqueue(ctx, cfg, in, flux, band, nullptr, st, s, "hd_beer_flux_band");
+      });
 }
 
 int hd_beer_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                  const struct hd_beer_rays* rays, double* rad, int* status, void* stream) {
-  if (!ctx) return fail(nullptr, HD_EINVAL, "hd_beer_rays: null context");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!rays) return fail(ctx, HD_EINVAL, "hd_beer_rays: null ray config");
-  if (!rad && !rays->brad)
-    return fail(ctx, HD_EINVAL, "hd_beer_rays: rad and brad both NULL: nothing to compute");
-  if (rays->brad && !rays->weight) return fail(ctx, HD_EINVAL, "hd_beer_rays: brad needs weight");
-  if (rays->nray < 1 || !rays->umu)
-    return fail(ctx, HD_EINVAL, "hd_beer_rays: rays need nray >= 1 and umu");
-  if (rays->per_column != 0 && rays->per_column != 1)
-    return fail(ctx, HD_EINVAL, "hd_beer_rays: per_column=%d must be 0 or 1", rays->per_column);
-  if (!(rays->alpha >= 0.0) || !std::isfinite(rays->alpha))
-    return fail(ctx, HD_EINVAL, "hd_beer_rays: alpha=%g must be finite and >= 0", rays->alpha);
-  int rc = validate(ctx, cfg, in, rad ? rad : rays->brad, "hd_beer_rays");
-  if (rc) return rc;
-  if ((long)in->nwave * in->ncol == 0) return HD_OK;
-  return run_solve(ctx, status, stream, "hd_beer_rays", [&](int*& st, hipStream_t s) {
-    return beer_enqueue(ctx, cfg, in, rad, nullptr, rays, st, s, "hd_beer_rays");
-  });
+  return solve_entry(
+      ctx, "hd_beer_rays", in, status, stream,
+      [&] {
+        if (!rays) return fail(ctx, HD_EINVAL, "hd_beer_rays: null ray config");
+        if (!rad && !rays->brad)
+          return fail(ctx, HD_EINVAL, "hd_beer_rays: rad and brad both NULL: nothing to compute");
+        if (rays->brad && !rays->weight)
+          return fail(ctx, HD_EINVAL, "hd_beer_rays: brad needs weight");
+        if (rays->nray < 1 || !rays->umu)
+          return fail(ctx, HD_EINVAL, "hd_beer_rays: rays need nray >= 1 and umu");
+        if (rays->per_column != 0 && rays->per_column != 1)
+          return fail(ctx, HD_EINVAL, "hd_beer_rays: per_column=%d must be 0 or 1",
+                      rays->per_column);
+        if (!(rays->alpha >= 0.0) || !std::isfinite(rays->alpha))
+          return fail(ctx, HD_EINVAL, "hd_beer_rays: alpha=%g must be finite and >= 0",
+                      rays->alpha);
+        return validate(ctx, cfg, in, rad, "hd_beer_rays", /*out_optional=*/true);
+      },
+      [&](int*& st, hipStream_t s) {
+        return beer_enqueue(ctx, cfg, in, rad, nullptr, rays, st, s, "hd_beer_rays");
+      });
 }
 
 }  // extern "C"

@@ -38,6 +38,7 @@
 
 #include "hd_beer.hpp"
 #include "hd_device.hpp"
+#include "hd_kernels.hpp"  // dispatch_nn
 
 #pragma clang fp contract(off)
 
@@ -564,20 +565,10 @@ __global__ __launch_bounds__(kAccThreads) void hd_beer_band_acc_staged_kernel(
 template <bool SURF>
 static hipError_t launch_beer_nn(int nn, const BeerArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)((a.nsc + 63) / 64)), block(64);
-#define HD_BEER_CASE(N)                                                                   \
-  case N:                                                                                 \
-    hipLaunchKernelGGL((hd_beer_flux_kernel<N, SURF>), grid, block, 0, stream, a);        \
-    break;
-  switch (nn) {
-    HD_BEER_CASE(1) HD_BEER_CASE(2) HD_BEER_CASE(3) HD_BEER_CASE(4) HD_BEER_CASE(5)
-    HD_BEER_CASE(6) HD_BEER_CASE(7) HD_BEER_CASE(8) HD_BEER_CASE(9) HD_BEER_CASE(10)
-    HD_BEER_CASE(11) HD_BEER_CASE(12) HD_BEER_CASE(13) HD_BEER_CASE(14) HD_BEER_CASE(15)
-    HD_BEER_CASE(16)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef HD_BEER_CASE
-  return hipGetLastError();
+  return dispatch_nn<1, kBeerMaxNN>(nn, [&](auto NN) {
+    hipLaunchKernelGGL((hd_beer_flux_kernel<NN, SURF>), grid, block, 0, stream, a);
+    return hipGetLastError();
+  });
 }
 
 // chunks of at most this many solves (under two one-lane waves per CU) take the team kernel

@@ -2083,23 +2083,6 @@ static void launch_sweep(const SweepArgs& sa, hipStream_t stream) {
 }
 
 template <int NN>
-static hipError_t launch_chunk(const PlanckArgs* pa, const TaucArgs* ta, const LayerArgs& la,
-                               const SweepArgs& sa, hipStream_t stream, hipEvent_t* ev) {
-  launch_prologue(pa, ta, stream);
-  const unsigned nb1 = (unsigned)(((la.nsc + 63) / 64) *
-                                  ((la.nlyr + kLayersPerBlock - 1) / kLayersPerBlock));
-  if (ev) (void)hipEventRecord(ev[0], stream);
-  if (la.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_layer_kernel<NN, true>), dim3(nb1), dim3(kLayerBlock), 0, stream, la);
-  else
-    hipLaunchKernelGGL((hd_layer_kernel<NN, false>), dim3(nb1), dim3(kLayerBlock), 0, stream, la);
-  if (ev) (void)hipEventRecord(ev[1], stream);
-  launch_sweep<NN>(sa, stream);
-  if (ev) (void)hipEventRecord(ev[2], stream);
-  return hipGetLastError();
-}
-
-template <int NN>
 static void launch_backsub(const SweepArgs& sa, hipStream_t stream, bool tail) {
   const dim3 gt((unsigned)((sa.nsc + 63) / 64)), gc((unsigned)((sa.nsc + 255) / 256));
   const bool nt = sa.nsc >= kNtMinSolves;
@@ -2125,18 +2108,10 @@ static void launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t
 }
 
 hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
-  switch (nn) {
-    case 1: launch_sweep_flx<1>(sa, fx, stream); break;
-    case 2: launch_sweep_flx<2>(sa, fx, stream); break;
-    case 3: launch_sweep_flx<3>(sa, fx, stream); break;
-    case 4: launch_sweep_flx<4>(sa, fx, stream); break;
-    case 5: launch_sweep_flx<5>(sa, fx, stream); break;
-    case 6: launch_sweep_flx<6>(sa, fx, stream); break;
-    case 7: launch_sweep_flx<7>(sa, fx, stream); break;
-    case 8: launch_sweep_flx<8>(sa, fx, stream); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    launch_sweep_flx<NN>(sa, fx, stream);
+    return hipGetLastError();
+  });
 }
 
 template <int NN>
@@ -2152,49 +2127,17 @@ static void launch_backsub_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream
 
 hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                  hipStream_t stream, bool tail) {
-  switch (nn) {
-    case 1: launch_backsub_flx<1>(sa, fx, stream, tail); break;
-    case 2: launch_backsub_flx<2>(sa, fx, stream, tail); break;
-    case 3: launch_backsub_flx<3>(sa, fx, stream, tail); break;
-    case 4: launch_backsub_flx<4>(sa, fx, stream, tail); break;
-    case 5: launch_backsub_flx<5>(sa, fx, stream, tail); break;
-    case 6: launch_backsub_flx<6>(sa, fx, stream, tail); break;
-    case 7: launch_backsub_flx<7>(sa, fx, stream, tail); break;
-    case 8: launch_backsub_flx<8>(sa, fx, stream, tail); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    launch_backsub_flx<NN>(sa, fx, stream, tail);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bool tail) {
-  switch (nn) {
-    case 1: launch_backsub<1>(sa, stream, tail); break;
-    case 2: launch_backsub<2>(sa, stream, tail); break;
-    case 3: launch_backsub<3>(sa, stream, tail); break;
-    case 4: launch_backsub<4>(sa, stream, tail); break;
-    case 5: launch_backsub<5>(sa, stream, tail); break;
-    case 6: launch_backsub<6>(sa, stream, tail); break;
-    case 7: launch_backsub<7>(sa, stream, tail); break;
-    case 8: launch_backsub<8>(sa, stream, tail); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_solve_chunk_nn(int nn, const PlanckArgs* pa, const TaucArgs* ta,
-                                 const LayerArgs& la, const SweepArgs& sa, hipStream_t stream,
-                                 hipEvent_t* ev) {
-  switch (nn) {
-    case 1: return launch_chunk<1>(pa, ta, la, sa, stream, ev);
-    case 2: return launch_chunk<2>(pa, ta, la, sa, stream, ev);
-    case 3: return launch_chunk<3>(pa, ta, la, sa, stream, ev);
-    case 4: return launch_chunk<4>(pa, ta, la, sa, stream, ev);
-    case 5: return launch_chunk<5>(pa, ta, la, sa, stream, ev);
-    case 6: return launch_chunk<6>(pa, ta, la, sa, stream, ev);
-    case 7: return launch_chunk<7>(pa, ta, la, sa, stream, ev);
-    case 8: return launch_chunk<8>(pa, ta, la, sa, stream, ev);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    launch_backsub<NN>(sa, stream, tail);
+    return hipGetLastError();
+  });
 }
 
 template <int NN>
@@ -2208,18 +2151,10 @@ static void launch_layer(const LayerArgs& la, hipStream_t stream) {
 }
 
 hipError_t launch_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
-  switch (nn) {
-    case 1: launch_layer<1>(la, stream); break;
-    case 2: launch_layer<2>(la, stream); break;
-    case 3: launch_layer<3>(la, stream); break;
-    case 4: launch_layer<4>(la, stream); break;
-    case 5: launch_layer<5>(la, stream); break;
-    case 6: launch_layer<6>(la, stream); break;
-    case 7: launch_layer<7>(la, stream); break;
-    case 8: launch_layer<8>(la, stream); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    launch_layer<NN>(la, stream);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_column_nn(int nn, const LayerArgs& la, const SweepArgs& sa, hipStream_t stream) {
 #if HD_AB_VARIANTS
@@ -2236,55 +2171,22 @@ hipError_t launch_column_nn(int nn, const LayerArgs& la, const SweepArgs& sa, hi
 }
 
 hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {
-  switch (nn) {
-    case 1: launch_sweep<1>(sa, stream); break;
-    case 2: launch_sweep<2>(sa, stream); break;
-    case 3: launch_sweep<3>(sa, stream); break;
-    case 4: launch_sweep<4>(sa, stream); break;
-    case 5: launch_sweep<5>(sa, stream); break;
-    case 6: launch_sweep<6>(sa, stream); break;
-    case 7: launch_sweep<7>(sa, stream); break;
-    case 8: launch_sweep<8>(sa, stream); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    launch_sweep<NN>(sa, stream);
+    return hipGetLastError();
+  });
 }
 
-// register path: records in 16-byte pairs (RecL / RecB), groups padded to even
-static size_t reg_pairs_l(int nn) {
-  const int nsym = nn * (nn + 1) / 2;
-  return (size_t)(2 * even_up(nsym) + 2 * even_up(nn) + 2) / 2;
-}
-static size_t reg_pairs_b(int nn) {
-  return (size_t)(even_up(nn * nn) + 2 * even_up(nn) + 2) / 2;
-}
-
-size_t layer_record_doubles(int nn) {
-  if (nn <= kMaxRegNN) return 2 * reg_pairs_l(nn);
-  return (size_t)(2 * nn * nn + 2 * nn + 2);  // team layout: full R, T rows (+ pad to even)
-}
-
-size_t bsub_record_doubles(int nn) {
-  if (nn <= kMaxRegNN) return 2 * reg_pairs_b(nn);
-  return (size_t)((nn * nn + 2 * nn + 2) & ~1);
-}
-
-size_t bsub_flx_record_doubles(int nn) {
-  if (nn <= kMaxRegNN) return 2 * reg_pairs_b(nn) + (size_t)even_up(nn) + 2;
-  return (size_t)((nn * nn + 3 * nn + 3) & ~1);  // team: the rh row and ch after cs
-}
-
+// the record sizes of hd_plan.hpp (host arithmetic) are those of the kernels' records
 static_assert(RecL<8>::pairs == 45 && RecB<8>::pairs == 41, "C4 record pairs");
 static_assert(RecBF<8>::pairs == 46 && RecBF<3>::pairs == RecB<3>::pairs + 3, "flx record pairs");
 
-size_t scratch_doubles_per_solve(int nn, int nlyr, bool planck) {
-  // every per-chunk region is double-buffered: chunk k+1's layer kernel (and its
-  // tauc/planck prologue) runs beside chunk k's sweep on another stream, and on
-  // the register path chunk k's back-substitution beside chunk k+1's layer
-  // kernel on a third (see hd_solve)
-  const size_t nb = 2;
-  return nb * (layer_record_doubles(nn) * nlyr + bsub_record_doubles(nn) * nlyr + 1 +
-               (planck ? (size_t)nlyr + 3 : 0) + (size_t)nlyr);
-}
+static_assert(layer_record_doubles(8) == 2 * RecL<8>::pairs &&
+                  layer_record_doubles(3) == 2 * RecL<3>::pairs &&
+                  bsub_record_doubles(8) == 2 * RecB<8>::pairs &&
+                  bsub_record_doubles(3) == 2 * RecB<3>::pairs &&
+                  bsub_flx_record_doubles(8) == 2 * RecBF<8>::pairs &&
+                  bsub_flx_record_doubles(3) == 2 * RecBF<3>::pairs,
+              "hd_plan.hpp record sizes");
 
 }  // namespace hd

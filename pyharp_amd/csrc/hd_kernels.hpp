@@ -4,14 +4,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "hd_device.hpp"
+#include "hd_plan.hpp"  // kMaxNN, kMaxRegNN, even_up, the record sizes, band_slots / band_steps
 
 namespace hd {
-
-constexpr int kMaxNN = 16;    // nstr <= 32
-constexpr int kMaxRegNN = 8;  // one-lane-per-problem kernels (hd_kernels.hip) up to nstr 16;
-                              // 16-lane team kernels (hd_team.hip) for nstr 18..32
 
 template <int NN>
 __host__ __device__ constexpr int ne1() {  // per-layer operator record (doubles)
@@ -24,8 +22,7 @@ __host__ __device__ constexpr int ne2() {  // per-level back-substitution record
 // Register-path flux records in 16-byte element pairs: [lc][pair][nsc] of
 // double2, so each lane moves two record elements per memory instruction (a
 // wave's 64 lanes: 1 KB contiguous).  Every group of elements starts at an even
-// element (padded), so a pair never spans two groups.
-__host__ __device__ constexpr int even_up(int n) { return (n + 1) & ~1; }
+// element (padded, even_up), so a pair never spans two groups.
 template <int NN>
 struct RecL {  // layer record: R~ upper | T~ upper | S~+ | S~- | tau'
   static constexpr int nsym = NN * (NN + 1) / 2;
@@ -307,15 +304,23 @@ __host__ __device__ constexpr int warm_bin(double x) {
 // host: the eigenvectors (row-major nn x nn, columns = vectors) of bin (ia, ib)
 void warm_eigvecs(int nn, const QuadHost& q, int ia, int ib, double* v);
 
+// The launchers' dispatch from a run-time nn to the kernel templates: f(integral_constant
+// <int, NN>) for the NN in [LO, HI] equal to nn; hipErrorInvalidValue for any other nn.
+template <int LO, int HI, class F>
+inline hipError_t dispatch_nn(int nn, F&& f) {
+  if constexpr (LO > HI) {
+    return hipErrorInvalidValue;
+  } else {
+    if (nn == LO) return f(std::integral_constant<int, LO>{});
+    return dispatch_nn<LO + 1, HI>(nn, f);
+  }
+}
+
 // copy the quadrature tables (index nn-1) into the current device's constant memory
 hipError_t upload_quad_tables(const QuadHost* per_nn);       // nn 1..kMaxRegNN
 hipError_t upload_quad_tables_team(const QuadHost* per_nn);  // nn kMaxRegNN+1..kMaxNN
 // cumulative scaled depth (beam) and level Planck radiances (planck) of a chunk
 void launch_prologue(const PlanckArgs* pa, const TaucArgs* ta, hipStream_t stream);
-// ev: 3 events (before K1, between, after K2) or nullptr; pa null when planck is off
-hipError_t launch_solve_chunk_nn(int nn, const PlanckArgs* pa, const TaucArgs* ta,
-                                 const LayerArgs& la, const SweepArgs& sa, hipStream_t stream,
-                                 hipEvent_t* ev);
 // back-substitution of a register-path chunk (reads sa.bsub / sa.xsurf)
 hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bool tail);
 // register path, separately: the layer kernel and the adding sweep of one chunk
@@ -332,22 +337,11 @@ hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                  hipStream_t stream, bool tail);
 hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                     hipStream_t stream);
-hipError_t launch_solve_chunk_team(int nn, const PlanckArgs* pa, const TaucArgs* ta,
-                                   const LayerArgs& la, const SweepArgs& sa, hipStream_t stream,
-                                   hipEvent_t* ev);
-// team path, separately: the layer kernel and the sweep of one chunk
+// team path: the layer kernel and the sweep of one chunk
 hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
 hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
-size_t scratch_doubles_per_solve(int nn, int nlyr, bool planck);
 // the chunk epilogue of hd_solve_band (after the chunk's back-substitution)
 hipError_t launch_band_reduce(const BandArgs& ba, hipStream_t stream);
-// column slots a 64-lane wave of consecutive column-major solves can touch
-inline int band_slots(int nwave) { return nwave >= 64 ? 2 : (63 / nwave + 2 < 64 ? 63 / nwave + 2 : 64); }
-inline int band_steps(int nwave) {
-  int k = 0;
-  while ((1 << k) < (nwave < 64 ? nwave : 64)) ++k;
-  return k;
-}
 // Kernel variants that were measured and not kept (the column
 // kernel, the LDS-state nstr-16 sweep, the one-wave team sweep, the VALU team layer
 // and sweep kernels, the per-angle radiance user kernel at nstr <= 16) are compiled
@@ -367,9 +361,5 @@ inline const char* ab_env(const char* name) {
 }
 // record an error for hd_last_error(NULL) (entry points without a context); returns code
 int set_global_error(int code, const char* fmt, ...);
-// doubles per (layer, solve) of the layer-operator and back-substitution records
-size_t layer_record_doubles(int nn);
-size_t bsub_record_doubles(int nn);
-size_t bsub_flx_record_doubles(int nn);  // hd_solve_flx's records (RecBF / the widened team record)
 
 }  // namespace hd

@@ -2027,39 +2027,17 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
 }
 
 hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_t stream) {
-  switch (nn) {
 #ifndef HD_RAD_WIDE
-    case 1: launch_rad<1>(a, radiances, stream); break;
-    case 2: launch_rad<2>(a, radiances, stream); break;
-    case 3: launch_rad<3>(a, radiances, stream); break;
-    case 4: launch_rad<4>(a, radiances, stream); break;
-    case 5: launch_rad<5>(a, radiances, stream); break;
-    case 6: launch_rad<6>(a, radiances, stream); break;
-    case 7: launch_rad<7>(a, radiances, stream); break;
-    case 8: launch_rad<8>(a, radiances, stream); break;
-    default: return wide::launch_rad_chunk(nn, a, radiances, stream);
+  if (nn > kMaxRegNN) return wide::launch_rad_chunk(nn, a, radiances, stream);
+  constexpr int lo = 1, hi = kMaxRegNN;
 #else
-    case 9: launch_rad<9>(a, radiances, stream); break;
-    case 10: launch_rad<10>(a, radiances, stream); break;
-    case 11: launch_rad<11>(a, radiances, stream); break;
-    case 12: launch_rad<12>(a, radiances, stream); break;
-    case 13: launch_rad<13>(a, radiances, stream); break;
-    case 14: launch_rad<14>(a, radiances, stream); break;
-    case 15: launch_rad<15>(a, radiances, stream); break;
-    case 16: launch_rad<16>(a, radiances, stream); break;
-    default: return hipErrorInvalidValue;
+  constexpr int lo = kMaxRegNN + 1, hi = kRadMaxNN;
 #endif
-  }
-  return hipGetLastError();
+  return dispatch_nn<lo, hi>(nn, [&](auto NN) {
+    launch_rad<NN>(a, radiances, stream);
+    return hipGetLastError();
+  });
 }
-
-#ifndef HD_RAD_WIDE
-size_t rad_scratch_doubles_per_unit(int nn, int nlyr) {
-  const size_t ne1r = (size_t)rad_layer_record_doubles(nn);
-  return (size_t)nlyr * (ne1r + rad_rec_doubles(nn) + rad_bsub_doubles(nn) + 4 * nn) +
-         (size_t)2 * nn;
-}
-#endif
 
 #ifdef HD_RAD_WIDE
 }  // namespace wide

@@ -143,7 +143,6 @@ hipError_t upload_rad_tables(const QuadHost* per_nn);  // nn 1..kRadMaxNN
 // tauc/planck prologue must have run (launch_prologue) for the chunk's solves;
 // radiances = false: fluxes at the user depths only (mode 0, no uu)
 hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_t stream);
-size_t rad_scratch_doubles_per_unit(int nn, int nlyr);
 // rays: out[i] = umu[i], or 1 where umu[i] is not a valid user cosine (not finite, 0 or
 // |umu| > 1), so the user-angle kernels never see such a value; hd_rad_ray_kernel reads
 // the caller's array, answers a bad ray with NaN and flags its solves

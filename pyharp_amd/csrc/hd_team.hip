@@ -608,44 +608,11 @@ static bool team_sweep_valu() {
 #endif
 }
 
-template <int NN>
-static hipError_t launch_team(const PlanckArgs* pa, const TaucArgs* ta, const LayerArgs& la,
-                              const SweepArgs& sa, hipStream_t stream, hipEvent_t* ev) {
-  static_assert(ne1t<NN>() % 2 == 0 && ne2t<NN>() % 2 == 0, "16-byte aligned records");
-  launch_prologue(pa, ta, stream);
-  const long nt1 = (long)la.nsc * la.nlyr;
-  const unsigned nb1 = (unsigned)((nt1 + kTeamsPerBlock - 1) / kTeamsPerBlock);
-  const unsigned nb2 = (unsigned)((sa.nsc + kTeamsPerBlock - 1) / kTeamsPerBlock);
-  // timing quadruple: layer start / end, sweep start / end
-  if (ev) (void)hipEventRecord(ev[0], stream);
-  if (team_layer_valu()) {
-#if HD_AB_VARIANTS
-    hipLaunchKernelGGL(hd_team_layer_kernel<NN>, dim3(nb1), dim3(kTeamBlock), 0, stream, la);
-#endif
-  } else {
-    const hipError_t e = launch_team_layer_mfma(NN, la, stream);
-    if (e != hipSuccess) return e;
-  }
-  if (ev) (void)hipEventRecord(ev[1], stream);
-  if (ev) (void)hipEventRecord(ev[2], stream);
-  if (!team_sweep_valu()) {
-    const hipError_t e = launch_team_sweep_mfma(NN, sa, stream);
-    if (ev) (void)hipEventRecord(ev[3], stream);
-    return e;
-  }
-#if HD_AB_VARIANTS
-  hipLaunchKernelGGL(hd_team_sweep_kernel<NN>, dim3(nb2), dim3(kTeamBlock), 0, stream, sa);
-#else
-  (void)nb2;
-#endif
-  if (ev) (void)hipEventRecord(ev[3], stream);
-  return hipGetLastError();
-}
-
-// the two halves of launch_team, for the pipelined multi-chunk path of hd_solve
-// (chunk k+1's layer kernel on one stream beside chunk k's sweep on another)
+// the layer kernel and the sweep of one chunk (hd_solve launches them on one stream, or
+// chunk k+1's layer kernel on one stream beside chunk k's sweep on another)
 template <int NN>
 static hipError_t launch_team_layer(const LayerArgs& la, hipStream_t stream) {
+  static_assert(ne1t<NN>() % 2 == 0 && ne2t<NN>() % 2 == 0, "16-byte aligned records");
 #if HD_AB_VARIANTS
   if (team_layer_valu()) {
     const long nt1 = (long)la.nsc * la.nlyr;
@@ -667,47 +634,13 @@ static hipError_t launch_team_sweep(const SweepArgs& sa, hipStream_t stream) {
 }
 
 hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_team_layer<9>(la, stream);
-    case 10: return launch_team_layer<10>(la, stream);
-    case 11: return launch_team_layer<11>(la, stream);
-    case 12: return launch_team_layer<12>(la, stream);
-    case 13: return launch_team_layer<13>(la, stream);
-    case 14: return launch_team_layer<14>(la, stream);
-    case 15: return launch_team_layer<15>(la, stream);
-    case 16: return launch_team_layer<16>(la, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_team_layer<NN>(la, stream); });
 }
 
 hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_team_sweep<9>(sa, stream);
-    case 10: return launch_team_sweep<10>(sa, stream);
-    case 11: return launch_team_sweep<11>(sa, stream);
-    case 12: return launch_team_sweep<12>(sa, stream);
-    case 13: return launch_team_sweep<13>(sa, stream);
-    case 14: return launch_team_sweep<14>(sa, stream);
-    case 15: return launch_team_sweep<15>(sa, stream);
-    case 16: return launch_team_sweep<16>(sa, stream);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_solve_chunk_team(int nn, const PlanckArgs* pa, const TaucArgs* ta,
-                                   const LayerArgs& la, const SweepArgs& sa, hipStream_t stream,
-                                   hipEvent_t* ev) {
-  switch (nn) {
-    case 9: return launch_team<9>(pa, ta, la, sa, stream, ev);
-    case 10: return launch_team<10>(pa, ta, la, sa, stream, ev);
-    case 11: return launch_team<11>(pa, ta, la, sa, stream, ev);
-    case 12: return launch_team<12>(pa, ta, la, sa, stream, ev);
-    case 13: return launch_team<13>(pa, ta, la, sa, stream, ev);
-    case 14: return launch_team<14>(pa, ta, la, sa, stream, ev);
-    case 15: return launch_team<15>(pa, ta, la, sa, stream, ev);
-    case 16: return launch_team<16>(pa, ta, la, sa, stream, ev);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_team_sweep<NN>(sa, stream); });
 }
 
 }  // namespace hd

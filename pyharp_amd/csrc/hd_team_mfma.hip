@@ -1922,17 +1922,8 @@ static hipError_t launch_sweep(const SweepArgs& sa, hipStream_t stream) {
 }
 
 hipError_t launch_team_sweep_mfma(int nn, const SweepArgs& sa, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_sweep<9>(sa, stream);
-    case 10: return launch_sweep<10>(sa, stream);
-    case 11: return launch_sweep<11>(sa, stream);
-    case 12: return launch_sweep<12>(sa, stream);
-    case 13: return launch_sweep<13>(sa, stream);
-    case 14: return launch_sweep<14>(sa, stream);
-    case 15: return launch_sweep<15>(sa, stream);
-    case 16: return launch_sweep<16>(sa, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_sweep<NN>(sa, stream); });
 }
 
 template <int NN>
@@ -1945,31 +1936,13 @@ static hipError_t launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipSt
 
 hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                     hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_sweep_flx<9>(sa, fx, stream);
-    case 10: return launch_sweep_flx<10>(sa, fx, stream);
-    case 11: return launch_sweep_flx<11>(sa, fx, stream);
-    case 12: return launch_sweep_flx<12>(sa, fx, stream);
-    case 13: return launch_sweep_flx<13>(sa, fx, stream);
-    case 14: return launch_sweep_flx<14>(sa, fx, stream);
-    case 15: return launch_sweep_flx<15>(sa, fx, stream);
-    case 16: return launch_sweep_flx<16>(sa, fx, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_sweep_flx<NN>(sa, fx, stream); });
 }
 
 hipError_t launch_team_layer_mfma(int nn, const LayerArgs& la, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_layer<9>(la, stream);
-    case 10: return launch_layer<10>(la, stream);
-    case 11: return launch_layer<11>(la, stream);
-    case 12: return launch_layer<12>(la, stream);
-    case 13: return launch_layer<13>(la, stream);
-    case 14: return launch_layer<14>(la, stream);
-    case 15: return launch_layer<15>(la, stream);
-    case 16: return launch_layer<16>(la, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_layer<NN>(la, stream); });
 }
 
 
@@ -2469,17 +2442,8 @@ static hipError_t launch_rad_user(const RadArgs& a, hipStream_t stream) {
 
 hipError_t launch_rad_team_user(int nn, const RadArgs& a, hipStream_t stream) {
   if (a.numu > rad_layer_record_doubles(nn)) return hipErrorInvalidValue;
-  switch (nn) {
-    case 9: return launch_rad_user<9>(a, stream);
-    case 10: return launch_rad_user<10>(a, stream);
-    case 11: return launch_rad_user<11>(a, stream);
-    case 12: return launch_rad_user<12>(a, stream);
-    case 13: return launch_rad_user<13>(a, stream);
-    case 14: return launch_rad_user<14>(a, stream);
-    case 15: return launch_rad_user<15>(a, stream);
-    case 16: return launch_rad_user<16>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_rad_user<NN>(a, stream); });
 }
 
 template <int NN>
@@ -2490,17 +2454,8 @@ static hipError_t launch_rad_sweep(const RadArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_rad_team_sweep(int nn, const RadArgs& a, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_rad_sweep<9>(a, stream);
-    case 10: return launch_rad_sweep<10>(a, stream);
-    case 11: return launch_rad_sweep<11>(a, stream);
-    case 12: return launch_rad_sweep<12>(a, stream);
-    case 13: return launch_rad_sweep<13>(a, stream);
-    case 14: return launch_rad_sweep<14>(a, stream);
-    case 15: return launch_rad_sweep<15>(a, stream);
-    case 16: return launch_rad_sweep<16>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_rad_sweep<NN>(a, stream); });
 }
 
 
@@ -2512,17 +2467,8 @@ static hipError_t launch_rad_layer(const RadArgs& a, hipStream_t stream) {
 }
 
 hipError_t launch_rad_team_layer(int nn, const RadArgs& a, hipStream_t stream) {
-  switch (nn) {
-    case 9: return launch_rad_layer<9>(a, stream);
-    case 10: return launch_rad_layer<10>(a, stream);
-    case 11: return launch_rad_layer<11>(a, stream);
-    case 12: return launch_rad_layer<12>(a, stream);
-    case 13: return launch_rad_layer<13>(a, stream);
-    case 14: return launch_rad_layer<14>(a, stream);
-    case 15: return launch_rad_layer<15>(a, stream);
-    case 16: return launch_rad_layer<16>(a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
+      nn, [&](auto NN) { return launch_rad_layer<NN>(a, stream); });
 }
 
 template <int NN>

@@ -10,8 +10,8 @@ set -e
 NAME=$1; shift
 OUT=ab_libs/obj_$NAME; mkdir -p $OUT
 C=pyharp_amd/csrc
-for src in hd_kernels.hip hd_team.hip hd_team_mfma.hip hd_rad.hip hd_harp.hip hd_api.cpp hd_ncread.cpp hd_rad_wide.hip; do
-  extra=""; [ $src = hd_team_mfma.hip ] && extra="-mllvm -disable-machine-licm"
+for src in hd_kernels.hip hd_team.hip hd_team_mfma.hip hd_rad.hip hd_harp.hip hd_api.cpp hd_ncread.cpp hd_rad_wide.hip hd_beer.hip; do
+  extra=""; [ $src = hd_team_mfma.hip -o $src = hd_beer.hip ] && extra="-mllvm -disable-machine-licm"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -x hip -DHD_AB_VARIANTS=1 "$@" $extra -c $C/$src -o $OUT/$src.o &
 done
 wait
