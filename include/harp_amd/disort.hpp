@@ -122,6 +122,9 @@ struct DisortOptions {
   HARP_AMD_ARG(std::vector<double>, user_mu) = {};
   HARP_AMD_ARG(std::vector<double>, user_phi) = {};
   HARP_AMD_ARG(int, device) = 0;
+  // planet radius for the 'spher' flag (pseudo-spherical beam), in the unit of the level
+  // altitudes zd passed to forward; unused without the flag, as in cdisort
+  HARP_AMD_ARG(double, radius) = 0.0;
 
  private:
   DisortState ds_;
@@ -222,8 +225,10 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     // harp's DISORT driver refuses ibcnd (src/rtsolver/rt_solver_disort.cpp_:67-68)
     TORCH_CHECK(!flags.count("ibcnd"), "RTSolverDisort::CalRadtranFlux: ibcnd = 1, expected 0 "
                 "(the special-case albedo/transmissivity mode is not supported)");
-    TORCH_CHECK(!flags.count("spher"), "Disort: flag 'spher': pseudo-spherical geometry is not "
-                "implemented");
+    spher_ = flags.count("spher") > 0;
+    TORCH_CHECK(!spher_ || (std::isfinite(options.radius()) && options.radius() > 0.0),
+                "Disort: flag 'spher': pseudo-spherical geometry needs DisortOptions.radius "
+                "(finite, > 0)");
     TORCH_CHECK(!flags.count("general_source"), "Disort: flag 'general_source': general "
                 "(user-supplied) sources are not implemented");
     TORCH_CHECK(!flags.count("output_uum"), "Disort: flag 'output_uum': per-mode intensities "
@@ -249,6 +254,8 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     // cdisort corrects with both flags; old_intensity_correction alone applies none
     corint_ = flags.count("intensity_correction") && flags.count("old_intensity_correction");
     radiance_ = !onlyfl_ || usrtau_;
+    TORCH_CHECK(!(spher_ && radiance_), "Disort: flag 'spher': pseudo-spherical radiances are "
+                "not implemented (set 'onlyfl', clear 'usrtau')");
     rad_ = torch::Tensor();
     auto& d = options.ds();
     if (radiance_) {
@@ -296,14 +303,21 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   //! temf is a Tensor (undefined = none) with a registered default, so
   //! torch::nn::AnyModule takes both forward(prop, &bc) and
   //! forward(prop, &bc, layer2level(...)) as radiation_band.cpp:124-127 calls them.
+  //! zd (with the 'spher' flag, and only then): the level altitudes above
+  //! options.radius(), bottom -> top, a float64 device tensor (nlyr+1) shared by all
+  //! columns or (ncol, nlyr+1) -- harp's x1f minus the planet radius (hd_solve_spher).
   torch::Tensor forward(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
-                        torch::Tensor temf = torch::Tensor()) {
+                        torch::Tensor temf = torch::Tensor(), torch::Tensor zd = torch::Tensor()) {
+    Sphere sp = sphere(prop, zd);
     Batch x = prepare(prop, bc, temf);
     const int nlev = radiance_ ? options.ds().ntau : x.nlyr + 1;
     auto flux = torch::empty({x.nwave, x.ncol, nlev, 2}, x.f64);
     auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
     int rc;
-    if (radiance_) {
+    if (spher_) {
+      rc = hd_solve_spher(context(x.dev.index()), &x.cfg, &x.in, &sp.s, nullptr,
+                          flux.data_ptr<double>(), nullptr, reinterpret_cast<void*>(stream));
+    } else if (radiance_) {
       auto const& d = options.ds();
       hd_radiance rad{usrtau_ ? d.ntau : 0, d.utau.data(), (int)umu_.size(), umu_.data(),
                       (int)phi_.size(), phi_.data(), x.bp("phi0"), onlyfl_ ? 1 : 0,
@@ -330,15 +344,21 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   //! boundaries, level 0 = surface: rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup,
   //! uavgso (hd_solve_flx).  CPU tensors are staged on the device with torch copies.
   torch::Tensor forward_flx(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
-                            torch::Tensor temf = torch::Tensor()) {
+                            torch::Tensor temf = torch::Tensor(),
+                            torch::Tensor zd = torch::Tensor()) {
     TORCH_CHECK(!usrtau_, "Disort.forward_flx: the flux record is at the layer boundaries "
                           "(clear the 'usrtau' flag)");
     TORCH_CHECK(onlyfl_, "Disort.forward_flx: a flux-only path (set the 'onlyfl' flag)");
+    Sphere sp = sphere(prop, zd);
     Batch x = prepare(prop, bc, temf, /*stage=*/true);
     auto flx = torch::empty({x.nwave, x.ncol, x.nlyr + 1, index::NFLX}, x.f64);
     auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
-    const int rc = hd_solve_flx(context(x.dev.index()), &x.cfg, &x.in, flx.data_ptr<double>(),
-                                nullptr, reinterpret_cast<void*>(stream));
+    const int rc =
+        spher_ ? hd_solve_flx_spher(context(x.dev.index()), &x.cfg, &x.in, &sp.s,
+                                    flx.data_ptr<double>(), nullptr,
+                                    reinterpret_cast<void*>(stream))
+               : hd_solve_flx(context(x.dev.index()), &x.cfg, &x.in, flx.data_ptr<double>(),
+                              nullptr, reinterpret_cast<void*>(stream));
     TORCH_CHECK(rc == HD_OK, "DisortWrapper::Run failed: ", hd_last_error(context(x.dev.index())));
     return x.in_dev.is_cuda() ? flx : flx.to(x.in_dev);
   }
@@ -347,8 +367,10 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   //! the solve (hd_solve_band): what examples/amars_lw.cpp:84-88 forms from
   //! forward's result, without storing the per-point fluxes
   torch::Tensor forward_band(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
-                             torch::Tensor temf, torch::Tensor weights) {
+                             torch::Tensor temf, torch::Tensor weights,
+                             torch::Tensor zd = torch::Tensor()) {
     TORCH_CHECK(!radiance_, "Disort.forward_band: the fused band sum is a flux-only path");
+    Sphere sp = sphere(prop, zd);
     Batch x = prepare(prop, bc, temf);
     auto w = weights.to(x.f64).reshape({-1}).contiguous();
     TORCH_CHECK(w.size(0) == x.nwave, "Disort.forward_band: ", w.size(0), " weights for ",
@@ -357,7 +379,9 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
     hd_band band{w.data_ptr<double>(), bflux.data_ptr<double>()};
     auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
     const int rc =
-        x.host ? hd_solve_band_host(context(x.dev.index()), &x.cfg, &x.in, w.data_ptr<double>(),
+        spher_ ? hd_solve_spher(context(x.dev.index()), &x.cfg, &x.in, &sp.s, &band, nullptr,
+                                nullptr, reinterpret_cast<void*>(stream))
+        : x.host ? hd_solve_band_host(context(x.dev.index()), &x.cfg, &x.in, w.data_ptr<double>(),
                                     bflux.data_ptr<double>(), nullptr, nullptr)
                : hd_solve_band(context(x.dev.index()), &x.cfg, &x.in, &band, nullptr, nullptr,
                                reinterpret_cast<void*>(stream));
@@ -389,11 +413,38 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   }
 
  protected:
-  FORWARD_HAS_DEFAULT_ARGS({2, torch::nn::AnyValue(torch::Tensor())})
+  FORWARD_HAS_DEFAULT_ARGS({2, torch::nn::AnyValue(torch::Tensor())},
+                           {3, torch::nn::AnyValue(torch::Tensor())})
 
  private:
   bool planck_ = false;
-  bool onlyfl_ = true, usrtau_ = false, radiance_ = false, corint_ = false;
+  bool onlyfl_ = true, usrtau_ = false, radiance_ = false, corint_ = false, spher_ = false;
+
+  // the 'spher' flag and zd come together, on the device (there are no host-array
+  // pseudo-spherical calls); z owns the memory s.zd refers to
+  struct Sphere {
+    hd_sphere s{};
+    torch::Tensor z;
+  };
+  Sphere sphere(torch::Tensor const& prop, torch::Tensor const& zd) const {
+    Sphere sp;
+    if (!spher_) {
+      TORCH_CHECK(!zd.defined(), "Disort.forward: zd given without the 'spher' flag (it would "
+                                 "be ignored)");
+      return sp;
+    }
+    TORCH_CHECK(zd.defined(), "Disort.forward: the 'spher' flag needs the level altitudes zd");
+    TORCH_CHECK(zd.scalar_type() == torch::kFloat64, "Disort.forward: zd must be a float64 tensor");
+    TORCH_CHECK(prop.device().is_cuda() && zd.device() == prop.device(),
+                "Disort.forward: 'spher' takes prop and zd on one HIP device");
+    const int nlyr = options.ds().nlyr;
+    TORCH_CHECK(prop.dim() == 4 && (zd.dim() == 1 || (zd.dim() == 2 && zd.size(0) == prop.size(1))) &&
+                    zd.size(-1) == nlyr + 1,
+                "Disort.forward: zd must be (nlyr+1) or (ncol, nlyr+1)");
+    sp.z = zd.contiguous();
+    sp.s = hd_sphere{options.radius(), sp.z.data_ptr<double>(), zd.dim() == 2 ? 1 : 0};
+    return sp;
+  }
   std::vector<double> umu_, phi_;
   torch::Tensor rad_;
 

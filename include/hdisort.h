@@ -61,10 +61,12 @@ extern "C" {
  * (required), onlyfl, planck, usrtau, usrang, intensity_correction +
  * old_intensity_correction, quiet, print-* are honoured (the full flux record of
  * hd_solve_flx -- cdisort's rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup, uavgso
- * at the layer boundaries -- with onlyfl and without usrtau); ibcnd is refused as
- * harp's driver refuses it (src/rtsolver/rt_solver_disort.cpp_:67-68), and so
- * are spher, general_source, output_uum and the new intensity correction
- * (not implemented); unknown names are refused. */
+ * at the layer boundaries -- with onlyfl and without usrtau); spher (pseudo-spherical
+ * beam geometry: hd_solve_spher / hd_solve_flx_spher) is honoured with onlyfl and
+ * without usrtau once a planet radius is configured, and refused otherwise; ibcnd is
+ * refused as harp's driver refuses it (src/rtsolver/rt_solver_disort.cpp_:67-68), and
+ * so are general_source, output_uum and the new intensity correction (not
+ * implemented); unknown names are refused. */
 
 /* return codes */
 #define HD_OK 0
@@ -219,6 +221,47 @@ typedef struct hd_band {
 
 int hd_solve_band(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
                   const hd_band *band, double *flux, int *status, void *stream);
+
+/*
+ * Pseudo-spherical beam geometry (cdisort's spher flag): the
+ * direct beam is attenuated along its true path through spherical shells -- the slant
+ * depth to level l is ch_l = sum_{j >= l} dtau_j g(l, j) with the geometric factor
+ *   g(l, j) = (2R + z_{j+1} + z_j) / (a(l, j+1) + a(l, j)),
+ *   a(l, m) = sqrt((z_m - z_l)(2R + z_m + z_l) + ((R + z_l) mu0)^2)
+ * (g = 1/mu0 as R -> infinity, g = 1 at mu0 = 1) -- while multiple scattering stays
+ * plane-parallel; inside a layer the beam is one exponential fitted to the slant depths
+ * at the layer's two boundaries (the layer-average secant of Dahlback & Stamnes 1991,
+ * not cdisort 2.1.3's exponential-linear fit: the two differ at second order in the
+ * layer thickness).  Level quantities: the direct flux mu0 F0 exp(-ch'_l) (ch' on the
+ * delta-M scaled depths), rfldir = mu0 F0 exp(-ch_l) (unscaled), uavgso = F0
+ * exp(-ch'_l) / (4 pi).  The horizontal-surface flux keeps the factor mu0 (cdisort's
+ * convention), so conservative scattering does not conserve rfldir + rfldn - flup here.
+ *   sph->radius      planet radius R > 0, in zd's unit (not finite or <= 0: HD_EINVAL)
+ *   sph->zd          DEVICE level altitudes above R, bottom -> top, strictly increasing:
+ *                    [nlyr+1] shared by all columns, or with per_column [ncol][nlyr+1]
+ *                    in temf's order (NULL: HD_EINVAL).  A column whose zd is not finite
+ *                    or not strictly increasing sets HD_STATUS_BAD_INPUT on its solves,
+ *                    which run with the beam off.
+ * umu0 in (0, 1] as hd_solve: a sun below the horizon stays HD_STATUS_BAD_INPUT.
+ * hd_solve_spher: hd_solve's fluxes (band NULL), or hd_solve_band's fused band sum
+ * (band given; flux may then be NULL); hd_solve_flx_spher: hd_solve_flx's record.
+ * Output layouts, status, stream, return codes, chunking and ordering on the context as
+ * those calls.  The plain kernels of either path only (every even nstr 2..32).  Under
+ * stream capture the calls never allocate: their scratch is larger than hd_solve's and
+ * hd_context_reserve does not size it, so a captured call returns HD_EINVAL unless an
+ * identical call outside capture came first.  There are no host-array variants.
+ */
+typedef struct hd_sphere {
+  double radius;
+  const double *zd; /* DEVICE [nlyr+1] or [ncol][nlyr+1], bottom->top */
+  int per_column;
+} hd_sphere;
+
+int hd_solve_spher(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                   const hd_sphere *sph, const hd_band *band /* or NULL */, double *flux,
+                   int *status, void *stream);
+int hd_solve_flx_spher(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                       const hd_sphere *sph, double *flx, int *status, void *stream);
 
 /*
  * The same two solves on HOST arrays (pydisort's own contract: CPU tensors in,

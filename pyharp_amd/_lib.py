@@ -28,7 +28,7 @@ EXPORTED = ("hd_version", "hd_last_error", "hd_context_create", "hd_context_dest
             "hd_context_get_timing",
             "hd_context_reserve", "hd_solve", "hd_solve_flx", "hd_solve_band", "hd_solve_host",
             "hd_solve_band_host", "hd_solve_radiance", "hd_solve_rays", "hd_quadrature",
-            "hd_chunk_solves")
+            "hd_chunk_solves", "hd_solve_spher", "hd_solve_flx_spher")
 
 # every symbol include/hdharp.h declares (harp-side steps around the solve)
 HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rfm_attenuate",
@@ -94,6 +94,10 @@ class HdBand(ctypes.Structure):
     _fields_ = [("weight", _dp), ("bflux", _dp)]
 
 
+class HdSphere(ctypes.Structure):
+    _fields_ = [("radius", ctypes.c_double), ("zd", _dp), ("per_column", ctypes.c_int)]
+
+
 class HdTiming(ctypes.Structure):
     _fields_ = [("layer_ms", ctypes.c_double), ("sweep_ms", ctypes.c_double),
                 ("layer_launches", ctypes.c_int), ("sweep_launches", ctypes.c_int)]
@@ -133,6 +137,13 @@ def load(path: str = LIB_PATH):
     lib.hd_solve_band.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                   ctypes.POINTER(HdInputs), ctypes.POINTER(HdBand),
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.hd_solve_spher.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                   ctypes.POINTER(HdInputs), ctypes.POINTER(HdSphere),
+                                   ctypes.POINTER(HdBand), ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p]
+    lib.hd_solve_flx_spher.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                       ctypes.POINTER(HdInputs), ctypes.POINTER(HdSphere),
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_solve_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                   ctypes.POINTER(HdInputs), ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_solve_band_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
@@ -253,6 +264,27 @@ class Context:
                                   ctypes.byref(band), ctypes.c_void_p(flux_ptr or 0),
                                   ctypes.c_void_p(status_ptr or 0),
                                   ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def solve_spher(self, cfg: HdConfig, inp: HdInputs, sph: HdSphere, band: HdBand | None,
+                    flux_ptr: int | None, status_ptr: int | None, stream_ptr: int | None):
+        """hd_solve_spher: hd_solve's fluxes (band None) or hd_solve_band's band sum with
+        the pseudo-spherical beam."""
+        rc = load().hd_solve_spher(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                   ctypes.byref(sph),
+                                   ctypes.byref(band) if band is not None else None,
+                                   ctypes.c_void_p(flux_ptr or 0),
+                                   ctypes.c_void_p(status_ptr or 0),
+                                   ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def solve_flx_spher(self, cfg: HdConfig, inp: HdInputs, sph: HdSphere, flx_ptr: int,
+                        status_ptr: int | None, stream_ptr: int | None):
+        """hd_solve_flx_spher: the flux record with the pseudo-spherical beam."""
+        rc = load().hd_solve_flx_spher(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                       ctypes.byref(sph), ctypes.c_void_p(flx_ptr),
+                                       ctypes.c_void_p(status_ptr or 0),
+                                       ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
     def solve_host(self, cfg: HdConfig, inp: HdInputs, flux_ptr: int):

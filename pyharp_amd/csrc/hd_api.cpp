@@ -655,6 +655,7 @@ struct SolveCall {
   double* flux;
   double* flx;
   const hd_band* band;
+  const hd_sphere* sph;  // pseudo-spherical beam (hd_solve_spher, hd_solve_flx_spher) or null
   int* status;
   hipStream_t stream;
   const char* who;  // the entry point in the messages
@@ -749,6 +750,16 @@ struct SolveCall {
     fx.lvl = at(hd::kRLvl, buf);
     return fx;
   }
+  // the chunk's slant depths and secants (hd_spher_kernel): sub-arrays of the region,
+  // interleaved with the chunk's own nsc
+  hd::SphArgs sph_args(int nsc, int buf) const {
+    double* q = at(hd::kRSph, buf);
+    hd::SphArgs sp{};
+    sp.chp = q;
+    sp.lam = q + (size_t)(nlyr + 2) * nsc;
+    sp.ch = flx ? q + (size_t)(2 * nlyr + 2) * nsc : nullptr;
+    return sp;
+  }
   hd::BandArgs band_args(long s0, int nsc, int buf) const {
     hd::BandArgs ba{};
     ba.part = at(hd::kRPart, 0);
@@ -771,6 +782,32 @@ struct SolveCall {
     const hd::PlanckArgs pa = planck_args(cfg, in, at(hd::kRPlanck, buf), s0, nsc, cmaj);
     const hd::TaucArgs ta = tauc_args(cfg, in, at(hd::kRTauc, buf), s0, nsc, cmaj);
     hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, st);
+    const hd::SphArgs sp = sph ? sph_args(nsc, buf) : hd::SphArgs{};
+    if (sph) {
+      hd::SpherProArgs xa{};
+      xa.prop = in->prop;
+      xa.fbeam = in->fbeam;
+      xa.umu0 = in->umu0;
+      xa.zd = sph->zd;
+      xa.chp = const_cast<double*>(sp.chp);
+      xa.lam = const_cast<double*>(sp.lam);
+      xa.ch = const_cast<double*>(sp.ch);
+      xa.dts = at(hd::kRSph, buf) + (size_t)(3 * nlyr + 3) * nsc;
+      xa.status = status;
+      xa.anyerr = ctx->anyerr;
+      xa.radius = sph->radius;
+      xa.s0 = s0;
+      xa.nsc = nsc;
+      xa.nlyr = nlyr;
+      xa.nprop = cfg->nprop;
+      xa.use_f = ta.use_f;
+      xa.f_slot = ta.f_slot;
+      xa.cmaj = cmaj;
+      xa.nwave = in->nwave;
+      xa.ncol = in->ncol;
+      xa.per_column = sph->per_column ? 1 : 0;
+      HD_HIP(ctx, hd::launch_spher_prologue(xa, st));
+    }
     if (!flx) return HD_OK;
     hd::FlxLevelArgs fa{};
     fa.prop = in->prop;
@@ -783,14 +820,23 @@ struct SolveCall {
     fa.nprop = cfg->nprop;
     fa.use_f = ta.use_f;
     fa.f_slot = ta.f_slot;
-    HD_HIP(ctx, hd::launch_flx_level(fa, st));
+    HD_HIP(ctx, sph ? hd::launch_flx_level_spher(fa, sp, st) : hd::launch_flx_level(fa, st));
     return HD_OK;
   }
-  // the path's kernels
-  hipError_t layer(const hd::LayerArgs& la, hipStream_t st) const {
+  // the path's kernels (pseudo-spherical: the SPHER instantiations of the plain ones)
+  hipError_t layer(const hd::LayerArgs& la, int buf, hipStream_t st) const {
+    if (sph)
+      return reg ? hd::launch_layer_spher_nn(nn, la, sph_args(la.nsc, buf), st)
+                 : hd::launch_team_layer_spher_nn(nn, la, sph_args(la.nsc, buf), st);
     return reg ? hd::launch_layer_nn(nn, la, st) : hd::launch_team_layer_nn(nn, la, st);
   }
   hipError_t sweep(const hd::SweepArgs& sa, int buf, hipStream_t st) const {
+    if (sph) {
+      const hd::FlxArgs fx = flx_args(buf);
+      return reg ? hd::launch_sweep_spher_nn(nn, sa, sph_args(sa.nsc, buf), flx ? &fx : nullptr, st)
+                 : hd::launch_team_sweep_spher_nn(nn, sa, sph_args(sa.nsc, buf),
+                                                  flx ? &fx : nullptr, st);
+    }
     if (reg)
       return flx ? hd::launch_sweep_flx_nn(nn, sa, flx_args(buf), st)
                  : hd::launch_sweep_nn(nn, sa, st);
@@ -832,7 +878,7 @@ int solve_one_chunk(const SolveCall& c) {
   hipEvent_t* ev;
   rc = timing_quad(c.ctx, &ev);
   if (rc) return rc;
-  hipError_t e = timed(ev, 0, c.stream, [&] { return c.layer(la, c.stream); });
+  hipError_t e = timed(ev, 0, c.stream, [&] { return c.layer(la, 0, c.stream); });
   if (e == hipSuccess) e = timed(ev, 2, c.stream, [&] { return c.sweep(sa, 0, c.stream); });
   if (e == hipSuccess && c.reg) e = c.backsub(sa, 0, c.stream, true);
   if (e == hipSuccess && c.band) e = hd::launch_band_reduce(c.band_args(0, nsc, 0), c.stream);
@@ -886,7 +932,7 @@ int solve_reg_pipeline(const SolveCall& c) {
     // the last reader of layer records[buf], is done
     if (c.need_pro) HD_HIP(ctx, hipStreamWaitEvent(lay, ctx->ev_pro[buf], 0));
     if (k >= 2) HD_HIP(ctx, hipStreamWaitEvent(lay, ctx->ev_sweep[buf], 0));
-    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, lay); });
+    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, buf, lay); });
     HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], lay));
     if (e != hipSuccess) return c.launch_failed(e);
     // sweep k on the caller's stream: after layer k, and after back-substitution
@@ -942,7 +988,7 @@ int solve_team_pipeline(const SolveCall& c) {
     hipEvent_t* ev;
     rc = timing_quad(ctx, &ev);
     if (rc) return rc;
-    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, lay); });
+    hipError_t e = timed(ev, 0, lay, [&] { return c.layer(la, buf, lay); });
     HD_HIP(ctx, hipEventRecord(ctx->ev_layer[buf], lay));
     if (e != hipSuccess) return c.launch_failed(e);
     HD_HIP(ctx, hipStreamWaitEvent(stream, ctx->ev_layer[buf], 0));
@@ -968,7 +1014,8 @@ int solve_team_pipeline(const SolveCall& c) {
 // and lay streams fork from it and join back into it).  flux / flx / band: hd_solve,
 // hd_solve_flx (flx alone) and hd_solve_band (band, flux optional).
 int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, double* flux,
-                  double* flx, const hd_band* band, int*& status, hipStream_t stream) {
+                  double* flx, const hd_band* band, int*& status, hipStream_t stream,
+                  const hd_sphere* sph = nullptr) {
   const long nsolve = (long)in->nwave * in->ncol;
   const int nn = cfg->nstr / 2;
   const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
@@ -976,12 +1023,15 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   const bool beam = in->fbeam != nullptr;
   const long chunk =
       ctx->chunk > 0 ? std::min(ctx->chunk, nsolve) : auto_chunk(nsolve, nn, cfg->nlyr, planck);
-  const bool beam_in_sweep = beam && !planck;
-  const bool need_tauc = beam && !beam_in_sweep;
-  const bool need_pro = planck || need_tauc;
+  // pseudo-spherical: the layer kernel always reads the prologue's secants and slant
+  // depths (its records carry the attenuated sources), never the plane-parallel depths
+  const bool beam_in_sweep = beam && !planck && !sph;
+  const bool need_tauc = beam && !beam_in_sweep && !sph;
+  const bool need_pro = planck || need_tauc || sph;
   const bool any_pro = need_pro || flx;
-  SolveCall c{ctx, cfg, in, flux, flx, band, status, stream,
-              /*who=*/flx ? "hd_solve_flx" : "hd_solve",
+  SolveCall c{ctx, cfg, in, flux, flx, band, sph, status, stream,
+              /*who=*/sph ? (flx ? "hd_solve_flx_spher" : "hd_solve_spher")
+                          : (flx ? "hd_solve_flx" : "hd_solve"),
               nsolve, chunk, nn, cfg->nlyr,
               /*nm=*/used_moments(cfg),
               /*cmaj=*/band && reg ? 1 : 0,
@@ -989,7 +1039,7 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
               planck, reg, beam_in_sweep, need_tauc, need_pro, any_pro,
               hd::SolvePlan(nn, cfg->nlyr, planck, flx != nullptr,
                             hd::band_scratch(nn, band != nullptr, flux != nullptr), in->nwave,
-                            chunk)};
+                            chunk, sph != nullptr)};
   int rc = ensure_scratch(ctx, c.who, c.plan.total);
   if (rc) return rc;
   rc = ensure_tables(ctx);
@@ -998,7 +1048,7 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   c.status = status;
   HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
   HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
-  if (reg && nn == 8 && ctx->column && !flx) return solve_column(c);
+  if (reg && nn == 8 && ctx->column && !flx && !sph) return solve_column(c);
   if (nsolve <= chunk) return solve_one_chunk(c);
   return reg ? solve_reg_pipeline(c) : solve_team_pipeline(c);
 }
@@ -1076,6 +1126,49 @@ int hd_solve_flx(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, dou
       },
       [&](int*& st, hipStream_t s) {
         return solve_enqueue(ctx, cfg, in, nullptr, flx, nullptr, st, s);
+      });
+}
+
+// pseudo-spherical geometry of a call: HD_EINVAL for what the host can see
+static int check_sphere(hd_context* ctx, const hd_sphere* sph, const char* who) {
+  if (!sph || !sph->zd) return fail(ctx, HD_EINVAL, "%s: sphere and its zd are required", who);
+  if (!std::isfinite(sph->radius) || !(sph->radius > 0.0))
+    return fail(ctx, HD_EINVAL, "%s: radius must be finite and > 0", who);
+  return HD_OK;
+}
+
+int hd_solve_spher(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                   const hd_sphere* sph, const hd_band* band, double* flux, int* status,
+                   void* stream) {
+  return solve_entry(
+      ctx, "hd_solve_spher", in, status, stream,
+      [&] {
+        if (band && (!band->weight || !band->bflux))
+          return fail(ctx, HD_EINVAL, "hd_solve_spher: band weights and bflux are required");
+        const int rc = check_sphere(ctx, sph, "hd_solve_spher");
+        if (rc) return rc;
+        return validate(ctx, cfg, in, flux, "hd_solve_spher", /*out_optional=*/band != nullptr);
+      },
+      [&](int*& st, hipStream_t s) {
+        return solve_enqueue(ctx, cfg, in, flux, nullptr, band, st, s, sph);
+      });
+}
+
+int hd_solve_flx_spher(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                       const hd_sphere* sph, double* flx, int* status, void* stream) {
+  return solve_entry(
+      ctx, "hd_solve_flx_spher", in, status, stream,
+      [&] {
+        int rc = check_sphere(ctx, sph, "hd_solve_flx_spher");
+        if (rc) return rc;
+        rc = validate(ctx, cfg, in, flx, "hd_solve_flx_spher");
+        if (rc || (long)in->nwave * in->ncol == 0) return rc;
+        if (reinterpret_cast<uintptr_t>(flx) % 16)
+          return fail(ctx, HD_EINVAL, "hd_solve_flx_spher: flx must be 16-byte aligned");
+        return HD_OK;
+      },
+      [&](int*& st, hipStream_t s) {
+        return solve_enqueue(ctx, cfg, in, nullptr, flx, nullptr, st, s, sph);
       });
 }
 

@@ -141,7 +141,10 @@ __global__ __launch_bounds__(256) void hd_tauc_kernel(TaucArgs A) {
 // sum), and (1 - ssa_in) 4 pi of the layer above the level (the top level: the top
 // layer; the input albedo, no dither, no scaling -- cdisort's layru at a boundary)
 // ============================================================================
-__global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
+// SPHER (hd_solve_flx_spher): the two beam terms on hd_spher_kernel's slant depths,
+// rfldir = mu0 F0 exp(-ch), uavgso = F0 exp(-ch') / (4 pi)
+template <bool SPHER>
+__device__ __forceinline__ void flx_level_body(const FlxLevelArgs& A, const SphArgs* P) {
   const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (sl >= A.nsc) return;
   const long s = A.s0 + sl;
@@ -150,7 +153,8 @@ __global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
   const double* p = A.prop + (size_t)s * L * np;
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
+  if constexpr (SPHER) beam = beam && P->chp[(size_t)(L + 1) * nsc + sl] != 0.0;
   const double rmu0 = beam ? 1.0 / mu0 : 0.0;
   const double f0mu0 = beam ? fb * mu0 : 0.0;
   const double f04pi = beam ? fb / (4.0 * kPi) : 0.0;
@@ -159,7 +163,18 @@ __global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
   double* o_abs = A.out + 2 * (size_t)(L + 1) * nsc;
   double tau = 0.0, tauc = 0.0, absl = 0.0;
   for (int lc = 0; lc <= L; ++lc) {  // solver order: top (harp layer L-1) first
-    if (lc < L) {
+    if constexpr (SPHER) {
+      o_dir[(size_t)lc * nsc + sl] = f0mu0 * exp(-P->ch[(size_t)lc * nsc + sl]);
+      o_so[(size_t)lc * nsc + sl] = f04pi * exp(-P->chp[(size_t)lc * nsc + sl]);
+      if (lc < L) {
+        const double a_in = np > 1 ? p[(size_t)(L - 1 - lc) * np + 1] : 0.0;
+        if (lc == 0) absl = (1.0 - a_in) * (4.0 * kPi);
+        o_abs[(size_t)lc * nsc + sl] = absl;
+        absl = (1.0 - a_in) * (4.0 * kPi);
+      } else {
+        o_abs[(size_t)lc * nsc + sl] = absl;
+      }
+    } else if (lc < L) {
       const double* q = p + (size_t)(L - 1 - lc) * np;
       const double a_in = np > 1 ? q[1] : 0.0;
       if (lc == 0) absl = (1.0 - a_in) * (4.0 * kPi);
@@ -176,6 +191,100 @@ __global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
       o_so[(size_t)lc * nsc + sl] = f04pi * exp(-tauc * rmu0);
       o_abs[(size_t)lc * nsc + sl] = absl;
     }
+  }
+}
+__global__ __launch_bounds__(256) void hd_flx_level_kernel(FlxLevelArgs A) {
+  flx_level_body<false>(A, nullptr);
+}
+__global__ __launch_bounds__(256) void hd_flx_level_spher_kernel(FlxLevelArgs A, SphArgs P) {
+  flx_level_body<true>(A, &P);
+}
+
+// ============================================================================
+// K0d (hd_solve_spher, hd_solve_flx_spher): pseudo-spherical beam geometry, one lane per
+// solve.  The slant optical depth to harp level l through the
+// spherical shells above it,
+//   ch_l = sum_{j >= l} dtau_j g(l, j),  g(l, j) = (2R + z_{j+1} + z_j) / (a(l, j+1) + a(l, j)),
+//   a(l, m) = sqrt((z_m - z_l)(2R + z_m + z_l) + ((R + z_l) mu0)^2)
+// (the argument of the root in this form has no cancellation; g -> 1/mu0 as R -> inf and
+// g = 1 at mu0 = 1), on the delta-M scaled layer depths (ch', what the solve uses) and,
+// for the flux record, on the unscaled ones (ch, rfldir only); and per solver layer the
+// secant lambda = (ch'_bottom - ch'_top) / dtau' of the beam's single exponential inside
+// it (dtau' = 0: g(j, j)).  lambda may be zero, negative or large.  A zd that is not
+// finite, not strictly increasing or reaches the planet's centre sets kStBadInput on the
+// solve and turns its beam off (row nlyr+1 of chp).
+// ============================================================================
+__global__ __launch_bounds__(256) void hd_spher_kernel(SpherProArgs A) {
+  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= A.nsc) return;
+  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
+  const int L = A.nlyr, np = A.nprop;
+  const size_t nsc = A.nsc;
+  const long col = s % A.ncol;
+  const double* z = A.zd + (A.per_column ? (size_t)col * (L + 1) : 0);
+  const double R = A.radius;
+  bool ok = R + z[0] > 0.0;
+  for (int m = 0; m <= L; ++m) {
+    const double zm = z[m];
+    if (!isfinite(zm) || (m > 0 && !(zm > z[m - 1]))) ok = false;
+  }
+  if (!ok) {
+    atomicOr(&A.status[s], kStBadInput);
+    atomicOr(A.anyerr, 1);
+  }
+  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
+  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
+  const bool beam = ok && fb > 0.0 && mu0 > 0.0;
+  A.chp[(size_t)(L + 1) * nsc + sl] = beam ? 1.0 : 0.0;
+  A.chp[sl] = 0.0;
+  if (A.ch) A.ch[sl] = 0.0;
+  if (!beam) {
+    for (int lc = 0; lc < L; ++lc) {
+      A.chp[(size_t)(lc + 1) * nsc + sl] = 0.0;
+      A.lam[(size_t)lc * nsc + sl] = 0.0;
+      if (A.ch) A.ch[(size_t)(lc + 1) * nsc + sl] = 0.0;
+    }
+    return;
+  }
+  // the layer depths by solver layer (top first), staged solve-interleaved: the double
+  // loop below reads them coalesced
+  double* dtp = A.dts;
+  double* dtu = A.dts + (size_t)L * nsc;
+  {
+    const double* p = A.prop + (size_t)s * L * np;
+    for (int lc = 0; lc < L; ++lc) {
+      const double* q = p + (size_t)(L - 1 - lc) * np;
+      double a = np > 1 ? q[1] : 0.0;
+      if (a == 1.0) a = 1.0 - kDither;
+      const double f = A.use_f ? q[A.f_slot] : 0.0;
+      dtp[(size_t)lc * nsc + sl] = (1.0 - a * f) * q[0];
+      dtu[(size_t)lc * nsc + sl] = q[0];
+    }
+  }
+  double chp_top = 0.0;
+  for (int lv = 1; lv <= L; ++lv) {  // solver level lv = harp level l = L - lv
+    const int l = L - lv;
+    const double zl = z[l];
+    const double rm = (R + zl) * mu0;
+    const double rm2 = rm * rm;
+    double a0 = rm;  // a(l, l)
+    double sp = 0.0, su = 0.0, g0 = 0.0;
+    double zj = zl;
+    for (int j = l; j < L; ++j) {  // harp layer j = solver layer L-1-j
+      const double zj1 = z[j + 1];
+      const double a1 = sqrt(fma(zj1 - zl, 2.0 * R + zj1 + zl, rm2));
+      const double g = (2.0 * R + zj1 + zj) / (a1 + a0);
+      if (j == l) g0 = g;
+      sp = fma(dtp[(size_t)(L - 1 - j) * nsc + sl], g, sp);
+      if (A.ch) su = fma(dtu[(size_t)(L - 1 - j) * nsc + sl], g, su);
+      a0 = a1;
+      zj = zj1;
+    }
+    A.chp[(size_t)lv * nsc + sl] = sp;
+    if (A.ch) A.ch[(size_t)lv * nsc + sl] = su;
+    const double dt = dtp[(size_t)(lv - 1) * nsc + sl];
+    A.lam[(size_t)(lv - 1) * nsc + sl] = dt > 0.0 ? (sp - chp_top) / dt : g0;
+    chp_top = sp;
   }
 }
 
@@ -220,10 +329,15 @@ struct ColRec {
 // (PairOut: RecL in HBM; ColRec: on chip).  psi_lds: this wave's Psi^T
 // staging, element e of lane lt at e * kLayerBlock + lt.  Returns the status bits.
 // OPQ: the quadrature table through quad_opaque (the column kernel's layer loop)
-template <int NN, bool OPQ, class Out>
+// SPHER (pseudo-spherical beam): the beam's secant in this layer
+// is hd_spher_kernel's lambda (any sign, or zero) in place of 1/mu0, its amplitude at the
+// layer top exp(-ch'_top) and its transmission exp(-(ch'_bottom - ch'_top)); the phase
+// function keeps the true mu0
+template <int NN, bool OPQ, class Out, bool SPHER = false>
 __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, int lc,
                                           double* psi_lds, int lt, Out& out,
-                                          const double* pf = nullptr, float* pf_sink = nullptr) {
+                                          const double* pf = nullptr, float* pf_sink = nullptr,
+                                          const SphArgs* P = nullptr) {
   constexpr int N = 2 * NN;
   constexpr int kPsi = psi_doubles<NN>();
   const Quad<NN>& Qc = OPQ ? quad_opaque<NN>() : quad<NN>();
@@ -246,9 +360,13 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
   if (fb > 0.0 && !(mu0 > 0.0 && mu0 <= 1.0)) st |= kStBadInput;  // cdisort c_chekin
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  if constexpr (SPHER) {
+    beam = beam && P->chp[(size_t)(L + 1) * A.nsc + sl] != 0.0;
+    rmu0 = beam ? P->lam[(size_t)lc * A.nsc + sl] : 0.0;
+  }
   const double mub = beam ? mu0 : 0.0;
 
   // ---- phase matrix even/odd parts (-A+ in ap, -A- in lch, upper) and the
@@ -488,15 +606,24 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
     lower_t_solve<NN>(lch, rdl, y);
     // scaled depth of the layer top; without the prologue's depths the beam is
     // taken as unit at the top and the sweep applies exp(-tau_c/mu0)
-    const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
-    const double att = 0.5 * exp(-tauc * rmu0);
+    double att;
+    if constexpr (SPHER) {
+      const double ct = P->chp[(size_t)lc * A.nsc + sl];
+      att = 0.5 * exp(-ct);
+      // a layer of zero depth leaves the diffuse field alone (the beam below it still
+      // changes: the sweep takes that from ch' of the next level)
+      e0 = taup > 0.0 ? exp(ct - P->chp[(size_t)(lc + 1) * A.nsc + sl]) : 1.0;
+    } else {
+      const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
+      att = 0.5 * exp(-tauc * rmu0);
+    }
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
       const double dd = Qc.rg[i] * fma(-y[i], rmu0, lxd[i]);  // (sd/w)(lxd - y/mu0)
       zp[i] = (sv[i] + dd) * att;
       zm[i] = (sv[i] - dd) * att;
     }
-    e0 = exp(-taup * rmu0);
+    if constexpr (!SPHER) e0 = exp(-taup * rmu0);
   } else {
 #pragma unroll
     for (int i = 0; i < NN; ++i) zp[i] = zm[i] = 0.0;
@@ -690,16 +817,71 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
       pf = A.prop + ((size_t)s2 * A.nlyr + (A.nlyr - 1 - lc2)) * A.nprop;
     }
   }
-  const int st = layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink);
+  const int st =
+      layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink);
 #else
-  const int st = layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out);
+  const int st =
+      layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out);
 #endif
   if (st) {
     atomicOr(&A.status[s], st);
     if (st & 0x0F) atomicOr(A.anyerr, 1);
   }
 }
-
+// hd_solve_spher / hd_solve_flx_spher: hd_layer_kernel with the pseudo-spherical beam.  The
+// block numbering and prefetch are repeated here rather than shared through a function:
+// called through one, hd_layer_kernel<4> and <5> compiled to other SGPR counts
+template <int NN, bool NT>
+__global__ __launch_bounds__(kLayerBlock) void hd_layer_spher_kernel(LayerArgs A, SphArgs P) {
+  __shared__ double psi_lds[psi_doubles<NN>() * kLayerBlock];  // Psi^T staged per lane
+  // block = 64 consecutive solves (one wave each) x kLayersPerBlock consecutive
+  // layers: a wave's stores are coalesced (same layer, consecutive solves).
+  // Neighbouring layers of a solve share 128-B lines of prop (18 doubles per
+  // record), so the blocks of one solve tile are numbered layer-fastest and
+  // dealt to the same XCD (blocks b and b + 8 share an XCD's L2): the second
+  // reader of a line finds it in L2 instead of HBM
+  const int lt = threadIdx.x;
+  const int ntl = (A.nlyr + kLayersPerBlock - 1) / kLayersPerBlock;
+  const int nb = (int)gridDim.x;
+  auto tile_of = [&](int b, int& ts, int& tl) {
+    const int x = b & 7, base = nb >> 3, extra = nb & 7;
+    const int logical = x * base + (x < extra ? x : extra) + (b >> 3);
+    ts = logical / ntl;
+    tl = logical - ts * ntl;
+  };
+  int ts, tl;
+  tile_of((int)blockIdx.x, ts, tl);
+  const int sl = ts * 64 + (lt & 63);
+  const int lc = tl * kLayersPerBlock + (lt >> 6);  // solver layer, 0 = top
+  if (sl >= A.nsc || lc >= A.nlyr) return;
+  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
+  PairOutT<NT> out{reinterpret_cast<double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * A.nsc + sl,
+                   (size_t)A.nsc, 0.0};
+#if HD_LAYER_PREFETCH
+  __shared__ float pf_sink[kLayerBlock];
+  const double* pf = nullptr;
+  if ((int)blockIdx.x + HD_LAYER_PREFETCH < nb) {
+    int ts2, tl2;
+    tile_of((int)blockIdx.x + HD_LAYER_PREFETCH, ts2, tl2);
+    int sl2 = ts2 * 64 + (lt & 63);
+    const int lc2 = tl2 * kLayersPerBlock + (lt >> 6);
+    if (sl2 >= A.nsc) sl2 = A.nsc - 1;
+    if (lc2 < A.nlyr) {
+      const long s2 = solve_of(A.s0 + sl2, A.cmaj, A.nwave, A.ncol);
+      pf = A.prop + ((size_t)s2 * A.nlyr + (A.nlyr - 1 - lc2)) * A.nprop;
+    }
+  }
+  const int st =
+      layer_body<NN, false, PairOutT<NT>, true>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink, &P);
+#else
+  const int st =
+      layer_body<NN, false, PairOutT<NT>, true>(A, s, sl, lc, psi_lds, lt, out, nullptr, nullptr, &P);
+#endif
+  if (st) {
+    atomicOr(&A.status[s], st);
+    if (st & 0x0F) atomicOr(A.anyerr, 1);
+  }
+}
 // ============================================================================
 // K2: per-solve adding sweep + back-substitution
 // ============================================================================
@@ -729,9 +911,12 @@ __device__ __forceinline__ void flx_emit(const FlxArgs& F, long s, long sl, size
 // x; returns the status bits.
 // FLX (hd_solve_flx): the records are RecBF -- each level also gets the mean-intensity
 // row rh and scalar ch -- and the surface level's eight components go to F->flx.
-template <int NN, bool NT, bool FLX = false, class RecAt>
+// SPHER (pseudo-spherical beam): the direct beam at every level is exp(-ch') of
+// hd_spher_kernel's slant depth, not exp(-tau_c/mu0) of the running depth; the layer
+// records carry the attenuated sources (beam_scale off)
+template <int NN, bool NT, bool FLX = false, bool SPHER = false, class RecAt>
 __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, RecAt&& rec_at,
-                                          const FlxArgs* F = nullptr) {
+                                          const FlxArgs* F = nullptr, const SphArgs* P = nullptr) {
   const Quad<NN>& Qc = quad<NN>();
   const int L = A.nlyr;
   const size_t nsc = A.nsc;
@@ -740,7 +925,8 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
+  if constexpr (SPHER) beam = beam && P->chp[(size_t)(L + 1) * nsc + sl] != 0.0;
   const double alb = A.albedo ? A.albedo[s] : 0.0;
   if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
   double top = A.fisot ? A.fisot[s] : 0.0;
@@ -752,6 +938,11 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
   const double twopi = 2.0 * kPi;
   const double rmu0 = beam ? 1.0 / mu0 : 0.0;
   const double f0mu0 = beam ? fb * mu0 : 0.0;
+  // direct beam at solver level lc (1 without a beam)
+  auto beam_at = [&](int lc, double tauc) {
+    if constexpr (SPHER) return beam ? exp(-P->chp[(size_t)lc * nsc + sl]) : 1.0;
+    else return exp(-tauc * rmu0);
+  };
 
   double ra[NN][NN];  // reflection of the stack above (upper triangle)
   double sd[NN];      // diffuse downward source at the current interface
@@ -780,7 +971,7 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
       for (int i = 0; i < NN; ++i) spl[i] = rec(RL::Sp + i);
     }
     // direct beam at the layer top; the sources of a unit-beam record scale with it
-    const double eb = exp(-tauc * rmu0);
+    const double eb = beam_at(lc, tauc);
     const double sscale = A.beam_scale ? eb : 1.0;
 #pragma unroll
     for (int i = 0; i < NN; ++i) spl[i] *= sscale;
@@ -978,7 +1169,7 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
     for (int j = 0; j < NN; ++j) grg += Qc.g[i] * HD_SYM(ra, i, j) * Qc.g[j];
   }
   double esurf = (1.0 - alb) * bsurf;
-  const double dirsurf = f0mu0 * exp(-tauc * rmu0);
+  const double dirsurf = f0mu0 * beam_at(L, tauc);
   if (beam) esurf += alb * dirsurf / kPi;
   const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
   double ip[NN];
@@ -1038,6 +1229,25 @@ __global__ __launch_bounds__(64) void hd_sweep_kernel(SweepArgs A) {
     return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
   };
   const int st = sweep_body<NN, NT>(A, sl, s, rec_at);
+  if (st) {
+    atomicOr(&A.status[s], st);
+    if (st & 0x0F) atomicOr(A.anyerr, 1);
+  }
+}
+
+// hd_solve_spher / hd_solve_flx_spher: the plain sweep with the pseudo-spherical beam
+template <int NN, bool NT, bool FLX>
+__global__ __launch_bounds__(64) void hd_sweep_spher_kernel(SweepArgs A, FlxArgs F, SphArgs P) {
+  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= A.nsc) return;
+  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
+  const size_t nsc = A.nsc;
+  auto rec_at = [&](int lc) {
+    const double2* lp =
+        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
+    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
+  };
+  const int st = sweep_body<NN, NT, FLX, true>(A, sl, s, rec_at, &F, &P);
   if (st) {
     atomicOr(&A.status[s], st);
     if (st & 0x0F) atomicOr(A.anyerr, 1);
@@ -2110,6 +2320,51 @@ static void launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t
 hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
   return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
     launch_sweep_flx<NN>(sa, fx, stream);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_spher_prologue(const SpherProArgs& pa, hipStream_t stream) {
+  hipLaunchKernelGGL(hd_spher_kernel, dim3((unsigned)((pa.nsc + 255) / 256)), dim3(256), 0, stream,
+                     pa);
+  return hipGetLastError();
+}
+
+hipError_t launch_flx_level_spher(const FlxLevelArgs& fa, const SphArgs& sp, hipStream_t stream) {
+  hipLaunchKernelGGL(hd_flx_level_spher_kernel, dim3((unsigned)((fa.nsc + 255) / 256)), dim3(256),
+                     0, stream, fa, sp);
+  return hipGetLastError();
+}
+
+template <int NN, bool FLX>
+static void launch_sweep_spher(const SweepArgs& sa, const FlxArgs& fx, const SphArgs& sp,
+                               hipStream_t stream) {
+  const dim3 g((unsigned)((sa.nsc + 63) / 64));
+  if (sa.nsc >= kNtMinSolves)
+    hipLaunchKernelGGL((hd_sweep_spher_kernel<NN, true, FLX>), g, dim3(64), 0, stream, sa, fx, sp);
+  else
+    hipLaunchKernelGGL((hd_sweep_spher_kernel<NN, false, FLX>), g, dim3(64), 0, stream, sa, fx, sp);
+}
+
+hipError_t launch_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp, const FlxArgs* fx,
+                                 hipStream_t stream) {
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    if (fx) launch_sweep_spher<NN, true>(sa, *fx, sp, stream);
+    else launch_sweep_spher<NN, false>(sa, FlxArgs{}, sp, stream);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp, hipStream_t stream) {
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    const unsigned nb1 = (unsigned)(((la.nsc + 63) / 64) *
+                                    ((la.nlyr + kLayersPerBlock - 1) / kLayersPerBlock));
+    if (la.nsc >= kNtMinSolves)
+      hipLaunchKernelGGL((hd_layer_spher_kernel<NN, true>), dim3(nb1), dim3(kLayerBlock), 0, stream,
+                         la, sp);
+    else
+      hipLaunchKernelGGL((hd_layer_spher_kernel<NN, false>), dim3(nb1), dim3(kLayerBlock), 0,
+                         stream, la, sp);
     return hipGetLastError();
   });
 }

@@ -264,6 +264,41 @@ struct FlxLevelArgs {
   int f_slot;  // prop slot of chi_nstr = 1 + nstr
 };
 
+// Pseudo-spherical beam geometry (hd_solve_spher, hd_solve_flx_spher; DESIGN.md section
+// 3e): what the SPHER instantiations of the layer, sweep and per-level kernels take beside
+// their own arguments -- the chunk's slant depths and layer secants from hd_spher_kernel
+struct SphArgs {
+  const double* chp;  // [nlyr+2][nsc]: delta-M scaled slant depth ch' to solver level lc
+                      // (0 = top, nlyr = surface); row nlyr+1: 1.0 where the solve's beam
+                      // is on (fbeam > 0, umu0 > 0 and a valid zd), else 0.0
+  const double* lam;  // [nlyr][nsc]: secant lambda of solver layer lc
+  const double* ch;   // [nlyr+1][nsc]: unscaled slant depth (hd_solve_flx_spher) or null
+};
+// prologue of a pseudo-spherical chunk: one lane per solve
+struct SpherProArgs {
+  const double* prop;
+  const double* fbeam;
+  const double* umu0;
+  const double* zd;  // [nlyr+1] or [ncol][nlyr+1], bottom -> top
+  double* chp;       // SphArgs::chp
+  double* lam;       // SphArgs::lam
+  double* ch;        // SphArgs::ch or null
+  double* dts;       // [2][nlyr][nsc] staging: scaled and unscaled layer depths by solver layer
+  int* status;
+  int* anyerr;
+  double radius;
+  long s0;
+  int nsc;
+  int nlyr;
+  int nprop;
+  int use_f;       // delta-M active (moments >= nstr available)
+  int f_slot;      // prop slot of chi_nstr = 1 + nstr
+  int cmaj;        // column-major chunk order (solve_of)
+  int nwave;
+  int ncol;
+  int per_column;  // zd per column
+};
+
 // chunk epilogue of the fused band sum: bflux[c] (=|+=) sum of the chunk's
 // partials of column c, in wave order (cmaj: register-path partials; else the
 // chunk flux buffer of the team path in wave-point order)
@@ -337,6 +372,18 @@ hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                  hipStream_t stream, bool tail);
 hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
                                     hipStream_t stream);
+// pseudo-spherical solves (hd_solve_spher, hd_solve_flx_spher): the chunk's prologue, then
+// the SPHER instantiations of the plain kernels of either path (fx null: the two fluxes;
+// the register path's back-substitutions are the plane-parallel ones)
+hipError_t launch_spher_prologue(const SpherProArgs& pa, hipStream_t stream);
+hipError_t launch_flx_level_spher(const FlxLevelArgs& fa, const SphArgs& sp, hipStream_t stream);
+hipError_t launch_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp, hipStream_t stream);
+hipError_t launch_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp, const FlxArgs* fx,
+                                 hipStream_t stream);
+hipError_t launch_team_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp,
+                                      hipStream_t stream);
+hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp,
+                                      const FlxArgs* fx, hipStream_t stream);
 // team path: the layer kernel and the sweep of one chunk
 hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
 hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);

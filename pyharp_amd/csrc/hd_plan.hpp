@@ -132,12 +132,19 @@ inline BandScratch band_scratch(int nn, bool band, bool caller_flux) {
 }
 
 enum SolveRegion { kRLayer, kRBsub, kRXsurf, kRPlanck, kRTauc, kRLvl, kRFsurf, kRPart, kRFchunk,
-                   kNSolveRegions };
+                   kRSph, kNSolveRegions };
+
+// doubles per solve of a pseudo-spherical chunk's prologue region (hd_spher_kernel):
+// ch' [nlyr+2] | lambda [nlyr] | ch [nlyr+1] | scaled and unscaled layer depths [2][nlyr]
+constexpr size_t spher_doubles(int nlyr) {
+  return (size_t)(nlyr + 2) + (size_t)nlyr + (size_t)(nlyr + 1) + 2 * (size_t)nlyr;
+}
 
 // Scratch regions, sized for the largest chunk so that no region moves between
 // chunks (inside a region the kernels interleave with the chunk's own nsc):
 //   layer ops[nb] | bsub[nb] | xsurf[nb] | planck[nb] | tauc[nb] | lvl[nb] (hd_solve_flx:
-//   the wider records and the per-level terms [3][nlyr+1]) | band epilogue
+//   the wider records and the per-level terms [3][nlyr+1]) | band epilogue | sph[nb]
+//   (pseudo-spherical plans only: the slant depths and secants, spher_doubles)
 // Chunk k uses buffer k & 1 of every per-chunk region (two chunks in flight).
 struct SolvePlan {
   size_t off[kNSolveRegions];  // doubles from the base to buffer 0
@@ -146,7 +153,8 @@ struct SolvePlan {
   size_t total;
   int nslot;  // column slots per wave of the fused band epilogue
 
-  SolvePlan(int nn, int nlyr, bool planck, bool flx, BandScratch band, int nwave, long chunk_) {
+  SolvePlan(int nn, int nlyr, bool planck, bool flx, BandScratch band, int nwave, long chunk_,
+            bool spher = false) {
     const size_t chunk = (size_t)chunk_, nlev2 = 2 * (size_t)(nlyr + 1);
     const size_t ne2 = flx ? bsub_flx_record_doubles(nn) : bsub_record_doubles(nn);
     nslot = band == kBandFused ? band_slots(nwave) : 0;
@@ -164,6 +172,7 @@ struct SolvePlan {
     } else if (band == kBandLocal) {
       len[kRFchunk] = chunk * nlev2;
     }
+    if (spher) len[kRSph] = spher_doubles(nlyr) * chunk;
     size_t q = 0;
     for (int r = 0; r < kNSolveRegions; ++r) off[r] = q, q += nbuf[r] * len[r];
     total = q;

@@ -213,9 +213,12 @@ __device__ __forceinline__ double team_matvec(const double (&xr)[NN], double x) 
 // ============================================================================
 // K1 (team, MFMA): per-(solve, layer) setup, four problems per wave
 // ============================================================================
-template <int NN, bool NT>
-__global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) {
-  __shared__ double lds[2 * kSet + 4 * 2 * 16];
+// SPHER (pseudo-spherical beam): as hd_kernels.hip's layer_body --
+// hd_spher_kernel's secant lambda in place of 1/mu0, exp(-ch'_top) at the layer top.
+// (The arguments by value and the LDS from the kernel: with LayerArgs by reference
+// hd_team_mfma_layer_kernel compiled to one or two more VGPRs at every NN.)
+template <int NN, bool NT, bool SPHER>
+__device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs* P, double* lds) {
   double* S0 = lds;
   double* S1 = lds + kSet;
   double* G = lds + 2 * kSet;  // [t][dsq | gsq][16]
@@ -268,9 +271,13 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
   if (fb > 0.0 && !(mu0 > 0.0 && mu0 <= 1.0)) st |= kStBadInput;  // cdisort c_chekin
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  if constexpr (SPHER) {
+    beam = beam && P->chp[(size_t)(L + 1) * A.nsc + sl] != 0.0;
+    rmu0 = beam ? P->lam[(size_t)lc * A.nsc + sl] : 0.0;
+  }
   const double mub = beam ? mu0 : 0.0;
 
   // ---- phase-matrix rows: S+ = -A+ (ap), S- = -A- (lch); beam source sums ----
@@ -468,13 +475,25 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
       const double sv = team_matvec<NN>(r_, ttv) * rg_i;
       get_rows<NN>(S0, t, i, r_);
       const double yy = team_matvec<NN>(r_, sd_i * mu_i * sv);
-      // tauc null: sources for a unit beam at the layer top (the sweep scales them)
-      const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
-      const double att = 0.5 * exp(-tauc * rmu0);
+      double att;
+      if constexpr (SPHER) {
+        const double ct = P->chp[(size_t)lc * A.nsc + sl];
+        att = 0.5 * exp(-ct);
+      } else {
+        // tauc null: sources for a unit beam at the layer top (the sweep scales them)
+        const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
+        att = 0.5 * exp(-tauc * rmu0);
+      }
       const double dd = rg_i * fma(-yy, rmu0, lxd);
       zp = (sv + dd) * att;
       zm = (sv - dd) * att;
-      e0 = exp(-taup * rmu0);
+      if constexpr (SPHER) {  // a layer of zero depth leaves the diffuse field alone
+        e0 = taup > 0.0 ? exp(P->chp[(size_t)lc * A.nsc + sl] -
+                              P->chp[(size_t)(lc + 1) * A.nsc + sl])
+                        : 1.0;
+      } else {
+        e0 = exp(-taup * rmu0);
+      }
     }
     get_m(S0, h, c, Y);            // W (M)
     mprod<false>(U, Y, X, h, c);   // U^T W
@@ -573,6 +592,17 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
     if (st & 0x0F) atomicOr(A.anyerr, 1);
   }
 }
+template <int NN, bool NT>
+__global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) {
+  __shared__ double lds[2 * kSet + 4 * 2 * 16];
+  team_mfma_layer_body<NN, NT, false>(A, nullptr, lds);
+}
+// hd_solve_spher / hd_solve_flx_spher: the team layer setup with the pseudo-spherical beam
+template <int NN, bool NT>
+__global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_spher_kernel(LayerArgs A, SphArgs P) {
+  __shared__ double lds[2 * kSet + 4 * 2 * 16];
+  team_mfma_layer_body<NN, NT, true>(A, &P, lds);
+}
 
 // ============================================================================
 // K2 (team, MFMA): adding sweep + back-substitution, four solves per wave.
@@ -593,9 +623,10 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) 
 // after cs (stride ne2tf), and the upward pass emits the eight components of every
 // level to F->flx instead of the two fluxes.
 // ============================================================================
-template <int NN, bool FLX>
+// SPHER (pseudo-spherical beam): the direct beam at every level from hd_spher_kernel's ch'.
+template <int NN, bool FLX, bool SPHER = false>
 __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const FlxArgs* F,
-                                                     double* lds) {
+                                                     double* lds, const SphArgs* P = nullptr) {
   constexpr int ne2 = FLX ? ne2tf<NN>() : ne2t<NN>();
   double* S0 = lds;
   double* S1 = lds + kSet;
@@ -623,7 +654,8 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
+  if constexpr (SPHER) beam = beam && P->chp[(size_t)(L + 1) * nsc + sl] != 0.0;
   const double alb = A.albedo ? A.albedo[s] : 0.0;
   if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
   double top = A.fisot ? A.fisot[s] : 0.0;
@@ -635,6 +667,11 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
   const double twopi = 2.0 * kPi;
   const double rmu0 = beam ? 1.0 / mu0 : 0.0;
   const double f0mu0 = beam ? fb * mu0 : 0.0;
+  // direct beam at solver level lc (1 without a beam)
+  auto beam_at = [&](int lc, double tauc) {
+    if constexpr (SPHER) return beam ? exp(-P->chp[(size_t)lc * nsc + sl]) : 1.0;
+    else return exp(-tauc * rmu0);
+  };
 
   // the wave's four solves in M layout: problem tt's records
   int slm[4];
@@ -676,7 +713,7 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
       tr[HD_K(J)] = rec[NN * NN + ii * NN + HD_K(J)] * msk;
     });
     // direct beam at the layer top; a unit-beam record's sources scale with it
-    const double eb = exp(-tauc * rmu0);
+    const double eb = beam_at(lc, tauc);
     const double sscale = A.beam_scale ? eb : 1.0;
     const double spl = rec[2 * NN * NN + ii] * msk * sscale;
     const double sml = rec[2 * NN * NN + NN + ii] * msk * sscale;
@@ -821,7 +858,7 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
   const double gsd = bc<0>(team_sum(g_i * sd));
   const double grg = bc<0>(team_sum(g_i * rgrow));
   double esurf = (1.0 - alb) * bsurf;
-  const double dirsurf = f0mu0 * exp(-tauc * rmu0);
+  const double dirsurf = f0mu0 * beam_at(L, tauc);
   if (beam) esurf += alb * dirsurf / kPi;
   const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
   double ip = g_i * x;
@@ -907,6 +944,13 @@ template <int NN>
 __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
   __shared__ double lds[2 * kSet];
   team_mfma_sweep_body<NN, true>(A, &F, lds);
+}
+// hd_solve_spher / hd_solve_flx_spher: the one-wave team sweep with the pseudo-spherical beam
+template <int NN, bool FLX>
+__global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_spher_kernel(SweepArgs A, FlxArgs F,
+                                                                         SphArgs P) {
+  __shared__ double lds[2 * kSet];
+  team_mfma_sweep_body<NN, FLX, true>(A, &F, lds, &P);
 }
 
 
@@ -1938,6 +1982,34 @@ hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& 
                                     hipStream_t stream) {
   return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
       nn, [&](auto NN) { return launch_sweep_flx<NN>(sa, fx, stream); });
+}
+
+hipError_t launch_team_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp,
+                                      hipStream_t stream) {
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NN) {
+    const unsigned nb1 = (unsigned)(((la.nsc + 3) / 4) * (long)la.nlyr);
+    if (la.nsc >= kNtMinSolves)
+      hipLaunchKernelGGL((hd_team_mfma_layer_spher_kernel<NN, true>), dim3(nb1), dim3(64), 0,
+                         stream, la, sp);
+    else
+      hipLaunchKernelGGL((hd_team_mfma_layer_spher_kernel<NN, false>), dim3(nb1), dim3(64), 0,
+                         stream, la, sp);
+    return hipGetLastError();
+  });
+}
+
+hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp,
+                                      const FlxArgs* fx, hipStream_t stream) {
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NN) {
+    const dim3 g((unsigned)((sa.nsc + 3) / 4));
+    if (fx)
+      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, true>), g, dim3(64), 0, stream, sa,
+                         *fx, sp);
+    else
+      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, false>), g, dim3(64), 0, stream, sa,
+                         FlxArgs{}, sp);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_team_layer_mfma(int nn, const LayerArgs& la, hipStream_t stream) {

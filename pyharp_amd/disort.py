@@ -51,8 +51,8 @@ _KNOWN_FLAGS = {
     "output_uum",
 }
 # cdisort flags this solver does not implement: rejected, never silently ignored
+# (spher: honoured by Disort.reset with a configured radius, onlyfl and no usrtau)
 _UNSUPPORTED_FLAGS = {
-    "spher": "pseudo-spherical geometry is not implemented",
     "general_source": "general (user-supplied) sources are not implemented",
     "output_uum": "per-mode intensities (uum) are not output",
 }
@@ -66,7 +66,8 @@ def check_flags(flags: set) -> None:
     harp's); cdisort's new (Buras-Emde-Dowling) intensity correction --
     ``intensity_correction`` without ``old_intensity_correction`` -- raises when
     radiances are requested (with ``onlyfl`` cdisort applies no correction, so the
-    flag has no effect there, as in examples/amarsw-ck.yaml:79-82)."""
+    flag has no effect there, as in examples/amarsw-ck.yaml:79-82).  ``spher`` is checked
+    by ``Disort.reset`` (it needs ``DisortOptions.radius``)."""
     unknown = flags - _KNOWN_FLAGS
     if unknown:
         raise RuntimeError(f"Disort: unknown flags {sorted(unknown)}")
@@ -205,6 +206,9 @@ class DisortOptions:
     user_mu = _arg("user_mu", list)
     user_phi = _arg("user_phi", list)
     device = _arg("device", 0)
+    # planet radius for the 'spher' flag (pseudo-spherical beam), in the unit of the level
+    # altitudes ``zd`` passed to forward; unused without the flag, as in cdisort
+    radius = _arg("radius", 0.0)
 
     def __init__(self):
         self._ds = _DisortState()
@@ -267,6 +271,16 @@ class Disort(RTSolver):
         self.usrtau = "usrtau" in flags
         self.usrang = "usrang" in flags
         self.radiance = (not self.onlyfl) or self.usrtau
+        # pseudo-spherical beam geometry: the flux paths only
+        self.spher = "spher" in flags
+        if self.spher:
+            r = float(op.radius())
+            if not (math.isfinite(r) and r > 0.0):
+                raise RuntimeError("Disort: flag 'spher': pseudo-spherical geometry needs "
+                                   "DisortOptions.radius (finite, > 0)")
+            if self.radiance:
+                raise RuntimeError("Disort: flag 'spher': pseudo-spherical radiances are not "
+                                   "implemented (set 'onlyfl', clear 'usrtau')")
         # Nakajima-Tanaka correction, TMS + IMS: cdisort applies it with both
         # intensity_correction and old_intensity_correction; old_intensity_correction
         # alone applies none (check_flags refuses the new method)
@@ -310,9 +324,13 @@ class Disort(RTSolver):
     # ------------------------------------------------------------------ #
     def forward(self, prop: torch.Tensor, bc: Optional[Dict[str, torch.Tensor]] = None,
                 temf: Optional[torch.Tensor] = None, *, status: Optional[torch.Tensor] = None,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None,
+                zd: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``zd`` (with the 'spher' flag, and only then): the level altitudes above
+        ``DisortOptions.radius``, bottom -> top, a float64 device tensor (nlyr+1,) shared by
+        all columns or (ncol, nlyr+1) -- harp's ``x1f`` minus the planet radius."""
         try:
-            return self._forward(prop, bc, temf, status=status, out=out)
+            return self._forward(prop, bc, temf, status=status, out=out, zd=zd)
         except RuntimeError as err:
             if "at least one solve failed" in str(err) and _beam_hint(bc):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
@@ -321,18 +339,21 @@ class Disort(RTSolver):
     def forward_band(self, prop: torch.Tensor, bc: Optional[Dict[str, torch.Tensor]] = None,
                      temf: Optional[torch.Tensor] = None, *, weights: torch.Tensor,
                      out: Optional[torch.Tensor] = None, flux: Optional[torch.Tensor] = None,
-                     status: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     status: Optional[torch.Tensor] = None,
+                     zd: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The band flux (ncol, nlyr+1, 2) = sum_w weights[w] F_w of this batch, with
         the sum fused into the solve (hd_solve_band): what every harp caller does
         with forward's result next (examples/amars_lw.cpp:84-88
         ``(flux * weights.view({-1,1,1,1})).sum(0)``; amars_sw.cpp:169-196 with
         weights = d(wavenumber)).  Per-point fluxes are stored only if ``flux``
-        (nwave, ncol, nlyr+1, 2) is given.  Fixed summation order, no atomics."""
+        (nwave, ncol, nlyr+1, 2) is given.  Fixed summation order, no atomics.  ``zd``: as
+        ``forward`` (the 'spher' flag)."""
         if self.radiance:
             raise RuntimeError("Disort.forward_band: the fused band sum is a flux-only path "
                                "(onlyfl without usrtau)")
         try:
-            return self._forward(prop, bc, temf, status=status, out=flux, band=(weights, out))
+            return self._forward(prop, bc, temf, status=status, out=flux, band=(weights, out),
+                                 zd=zd)
         except RuntimeError as err:
             if "at least one solve failed" in str(err) and _beam_hint(bc):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
@@ -341,20 +362,22 @@ class Disort(RTSolver):
     def forward_flx(self, prop: torch.Tensor, bc: Optional[Dict[str, torch.Tensor]] = None,
                     temf: Optional[torch.Tensor] = None, *,
                     status: Optional[torch.Tensor] = None,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None,
+                    zd: Optional[torch.Tensor] = None) -> torch.Tensor:
         """DISORT's full flux record at every level, (nwave, ncol, nlyr+1, NFLX) in the
         component order of cdisort's disort_radiant (index.IRFLDIR .. IUAVGSO): direct
         beam, diffuse down, up, flux divergence dF/dtau, mean intensity and its down /
         up / direct-beam parts (hd_solve_flx; definitions in include/hdisort.h).  Level
         0 is the surface.  On the input's device: CPU tensors are staged with torch
-        copies and the record comes back on the CPU."""
+        copies and the record comes back on the CPU.  ``zd``: as ``forward`` (the 'spher'
+        flag; rfldir then on the unscaled slant depth, uavgso on the scaled one)."""
         if self.usrtau:
             raise RuntimeError("Disort.forward_flx: the flux record is at the layer boundaries "
                                "(clear the 'usrtau' flag)")
         if not self.onlyfl:
             raise RuntimeError("Disort.forward_flx: a flux-only path (set the 'onlyfl' flag)")
         try:
-            return self._forward(prop, bc, temf, status=status, out=out, flx=True)
+            return self._forward(prop, bc, temf, status=status, out=out, flx=True, zd=zd)
         except RuntimeError as err:
             if "at least one solve failed" in str(err) and _beam_hint(bc):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
@@ -572,9 +595,34 @@ class Disort(RTSolver):
                             wave_upper=ptr(wu))
         return cfg, inp, keep
 
-    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None, flx=False):
+    def _check_sphere(self, prop, zd):
+        """The 'spher' flag and ``zd`` come together, on the device; returns the
+        hd_sphere of the call or None."""
+        if not self.spher:
+            if zd is not None:
+                raise RuntimeError("Disort.forward: zd given without the 'spher' flag (it would "
+                                   "be ignored)")
+            return None
+        if zd is None:
+            raise RuntimeError("Disort.forward: the 'spher' flag needs the level altitudes zd=")
+        nlyr = self.options.ds().nlyr
+        if not isinstance(zd, torch.Tensor) or zd.dtype != torch.float64:
+            raise RuntimeError("Disort.forward: zd must be a float64 tensor")
+        if prop.device.type != "cuda" or zd.device != prop.device:
+            raise RuntimeError("Disort.forward: 'spher' takes prop and zd on one HIP device "
+                               "(there are no host-array pseudo-spherical calls)")
+        if prop.dim() == 4 and (zd.dim() not in (1, 2) or zd.shape[-1] != nlyr + 1 or
+                                (zd.dim() == 2 and zd.shape[0] != prop.shape[1])):
+            raise RuntimeError(f"Disort.forward: zd must be (nlyr+1,) or (ncol, nlyr+1) = "
+                               f"({prop.shape[1]}, {nlyr + 1}), got {tuple(zd.shape)}")
+        z = zd.contiguous()
+        return _lib.HdSphere(radius=float(self.options.radius()), zd=z.data_ptr(),
+                             per_column=int(z.dim() == 2)), z
+
+    def _forward(self, prop, bc, temf, *, status=None, out=None, band=None, flx=False, zd=None):
         ds = self.options.ds()
         bc = {} if bc is None else bc
+        sph = self._check_sphere(prop, zd)
         nwave, ncol, nlyr, nprop, in_dev, dev = self._check_inputs(prop, bc, temf)
         f64 = torch.float64
         if (in_dev.type != "cuda" and not self.radiance and out is None and status is None
@@ -584,6 +632,9 @@ class Disort(RTSolver):
             # beside the solve of the previous piece
             return self._forward_host(prop, bc, temf, band, dev, nwave, ncol, nlyr, nprop)
         cfg, inp, keep = self._stage(prop, bc, temf, dev)
+        if sph is not None:
+            sph, zkeep = sph
+            keep.append(zkeep)
         nlev = ds.ntau if self.radiance else nlyr + 1
         ncomp = NFLX if flx else 2
         if out is None:
@@ -621,12 +672,26 @@ class Disort(RTSolver):
             keep.append(wts)
             hb = _lib.HdBand(weight=wts.data_ptr(), bflux=bout.data_ptr())
             with torch.cuda.device(dev):
-                _context(dev.index).solve_band(cfg, inp, hb, ptr(flux),
-                                               status.data_ptr() if status is not None else None,
-                                               stream.cuda_stream)
+                if sph is not None:
+                    _context(dev.index).solve_spher(
+                        cfg, inp, sph, hb, ptr(flux),
+                        status.data_ptr() if status is not None else None, stream.cuda_stream)
+                else:
+                    _context(dev.index).solve_band(
+                        cfg, inp, hb, ptr(flux),
+                        status.data_ptr() if status is not None else None, stream.cuda_stream)
             del keep
             return bout.to(in_dev) if in_dev.type != "cuda" else bout
-        if flx:
+        if sph is not None:
+            st = status.data_ptr() if status is not None else None
+            with torch.cuda.device(dev):
+                if flx:
+                    _context(dev.index).solve_flx_spher(cfg, inp, sph, flux.data_ptr(), st,
+                                                        stream.cuda_stream)
+                else:
+                    _context(dev.index).solve_spher(cfg, inp, sph, None, flux.data_ptr(), st,
+                                                    stream.cuda_stream)
+        elif flx:
             with torch.cuda.device(dev):
                 _context(dev.index).solve_flx(cfg, inp, flux.data_ptr(),
                                               status.data_ptr() if status is not None else None,
