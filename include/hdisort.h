@@ -86,7 +86,12 @@ extern "C" {
 #define HD_STATUS_EIGEN 0x02     /* eigenvalue <= 0 / Cholesky breakdown / Jacobi
                                     not converged within the sweep cap          */
 #define HD_STATUS_NONFINITE 0x04 /* NaN/Inf produced                             */
-#define HD_STATUS_RESONANCE 0x10 /* warning: umu0 ~ 1/k (beam/quadrature resonance) */
+#define HD_STATUS_RESONANCE 0x10 /* warning: umu0 within 1.5e-8 (relative) of 1/k of a
+                                    layer: that layer of this solve was solved for a beam
+                                    cosine moved to that distance from 1/k (the flux paths;
+                                    the fluxes move by < 1e-7 of their scale).  The radiance
+                                    and 'spher' paths clamp the one denominator instead
+                                    (within 5e-10) and lose that mode's beam source there */
 #define HD_STATUS_PIVOT 0x20     /* warning: tiny pivot in the boundary sweep      */
 #define HD_STATUS_ERROR_MASK 0x0F
 

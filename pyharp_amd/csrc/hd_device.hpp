@@ -36,6 +36,27 @@ constexpr double kDither = 4.712160915387242e-08;
 // the layer kernels run jacobi_os_polish
 constexpr double kResPolish = 3.0e-4;
 
+// Beam resonance.  Where |1/mu0^2 - k_j^2| < kResMove / mu0^2 for a
+// mode j of a layer, the flux layer kernels solve that layer for the secant
+// 1/mu0'^2 = k_j^2 (1 +- kResMove) (the side mu0 is on) wherever the resonant mode's
+// amplitude ~ 1 / (1/mu0'^2 - k_j^2) goes: every denominator, the difference part of the
+// particular solution and the beam's attenuation across the layer.  That is the exact
+// particular solution of a beam at mu0' up to a residual of relative size kResMove in the
+// source, so the flux moves by O(kResMove) and rounding is amplified by 1 / kResMove
+// (profiles/hard/threshold_sweep.txt).  Sets HD_STATUS_RESONANCE.
+constexpr double kResMove = 3.0e-8;
+// The clamp the radiance kernels (hd_rad.hip, hd_rad_team_layer_kernel) and the 'spher'
+// instantiations still use: the one denominator held at +-kResClamp / mu0^2 and nothing
+// else moved, which drops that mode's share of the beam source.
+constexpr double kResClamp = 1.0e-9;
+// Thin thermal layer: with a Planck source linear in tau the slope part of the source,
+// x = g 2 (dB / tau') h, is O(dB / tau') and Q~- = I - A- is O(tau'): formed as that
+// difference, Q~- x carries an error eps dB / tau' (1e-7 of the flux scale at tau' = 1e-5
+// under a 10 K step, everything at 1e-12).  In a layer of scaled depth 0 < tau' < kThinTau
+// the layer kernels take x through Q~- = A- Omega Omega^T instead, products only.
+// tau' = 0 carries the top level's value through, as before.
+constexpr double kThinTau = 1.0e-3;
+
 // per-thread status bits (mirrors include/hdisort.h)
 constexpr int kStBadInput = 0x01;
 constexpr int kStEigen = 0x02;

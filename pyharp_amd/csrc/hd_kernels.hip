@@ -549,20 +549,52 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   }
   // beam, the part that needs only B and k (before L is back: y2 dies first)
   double ybt[NN];  // B K^-1 tt, tt = V^T y2 / (1/mu0^2 - k^2), V = B K^-1
+  double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
   if (beam) {
     double tt[NN];
     const double r2 = rmu0 * rmu0;
+    bool near = false;  // a mode within kResMove of the resonance (hd_device.hpp)
 #pragma unroll
     for (int j = 0; j < NN; ++j) {
       double t = 0.0;
 #pragma unroll
       for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
       double den = fma(-kk[j], kk[j], r2);
-      if (fabs(den) < 1.0e-9 * r2) {
-        st |= kStResonance;
-        den = den < 0.0 ? -1.0e-9 * r2 : 1.0e-9 * r2;
+      if constexpr (SPHER) {
+        if (fabs(den) < kResClamp * r2) {
+          st |= kStResonance;
+          den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
+        }
+      } else {
+        near = near || fabs(den) < kResMove * r2;
       }
       tt[j] = t * (rk[j] * rk[j]) * rcp_nr(den);  // K^-1 (V^T y2 / den)
+    }
+    if constexpr (!SPHER) {
+      if (near) {
+        // the mode nearest the resonance sets the secant 1/mu0'^2, and tt is formed again
+        // with it (a second eigenvalue within kResMove of that mode would keep a small
+        // denominator: eigenvalues of a layer that close are not known to occur, and
+        // kStNonFinite would report it)
+        st |= kStResonance;
+        double dmin = 2.0 * r2, r2e = r2;
+#pragma unroll
+        for (int j = 0; j < NN; ++j) {
+          const double den = fma(-kk[j], kk[j], r2);
+          if (fabs(den) < dmin) {
+            dmin = fabs(den);
+            r2e = kk[j] * kk[j] * (den < 0.0 ? 1.0 - kResMove : 1.0 + kResMove);
+          }
+        }
+        rmu0e = sqrt(r2e);
+#pragma unroll
+        for (int j = 0; j < NN; ++j) {
+          double t = 0.0;
+#pragma unroll
+          for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
+          tt[j] = t * (rk[j] * rk[j]) * rcp_nr(fma(-kk[j], kk[j], r2e));
+        }
+      }
     }
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
@@ -619,11 +651,11 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
     }
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
-      const double dd = Qc.rg[i] * fma(-y[i], rmu0, lxd[i]);  // (sd/w)(lxd - y/mu0)
+      const double dd = Qc.rg[i] * fma(-y[i], rmu0e, lxd[i]);  // (sd/w)(lxd - y/mu0')
       zp[i] = (sv[i] + dd) * att;
       zm[i] = (sv[i] - dd) * att;
     }
-    if constexpr (!SPHER) e0 = exp(-taup * rmu0);
+    if constexpr (!SPHER) e0 = exp(-taup * rmu0e);
   } else {
 #pragma unroll
     for (int i = 0; i < NN; ++i) zp[i] = zm[i] = 0.0;
@@ -678,6 +710,30 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
     ga[i] = Qc.g[i] * (cvec[i] - fma(-zp[i], e0, zm[i]));
     gb[i] = Qc.g[i] * (fma(zp[i], e0, zm[i]) + bsum);
   }
+  // Thin thermal layer: x = g (2 dB/tau') h is O(dB / tau') and Q~- = I - A- is O(tau'),
+  // a difference of O(1) numbers.  Q~- = A- Omega Omega^T has no such difference: with
+  // w = Omega Omega^T x (O(dB)) and ga0 = g (dB - a) the rest,
+  // Q~- (ga0 + x) = ga0 - A- (ga0 - w): ga carries ga0 - w, and ga0 is formed again where
+  // p is (from zp, zm, e0, which live on to the sources), so nothing more than ga stays
+  // live across the factorisation.
+  const bool thin = A.planck && taup > 0.0 && taup < kThinTau;  // hd_device.hpp
+  if (thin) {
+    double y[NN];
+#pragma unroll
+    for (int j = 0; j < NN; ++j) {
+      double t = 0.0;  // x = g (cvec - dB): the slope part alone (|x| >> dB here)
+#pragma unroll
+      for (int i = 0; i < NN; ++i) t = fma(v[i][j], Qc.g[i] * (cvec[i] - db), t);
+      y[j] = t;
+    }
+#pragma unroll
+    for (int i = 0; i < NN; ++i) {
+      double t = 0.0;
+#pragma unroll
+      for (int j = 0; j < NN; ++j) t = fma(v[i][j], y[j], t);
+      ga[i] = Qc.g[i] * (db - fma(-zp[i], e0, zm[i])) - t;
+    }
+  }
   // By Woodbury, Q~- = Omega (I + Omega^T Omega)^-1 Omega^T = I - A-  and
   // Q~+ = -Psi^T (I + Psi Psi^T)^-1 Psi = A+ - I  with the SPD inverses
   // A- = (I + Omega Omega^T)^-1, A+ = (I + Psi^T Psi)^-1 (eigenvalues in (0, 1]),
@@ -702,6 +758,10 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
 #pragma unroll
       for (int j = 0; j < NN; ++j) t = fma(-HD_SYM(am_, i, j), ga[j], t);
       pvec[i] = t;
+    }
+    if (thin) {  // ga0 - A- ga: w = ga0 - ga back in
+#pragma unroll
+      for (int i = 0; i < NN; ++i) pvec[i] += Qc.g[i] * (db - fma(-zp[i], e0, zm[i])) - ga[i];
     }
   }
   double ap_[NN][NN], qvec[NN];
@@ -772,6 +832,10 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   // the pad after tau': the layer's direct-beam transmission e^(-tau'/mu0) (1
   // without a beam), from which hd_sweep_lean_kernel carries the beam down as a
   // running product instead of an exp of the running depth
+  // (the beam's own transmission, not the one of a secant moved off a resonance)
+  if constexpr (!SPHER) {
+    if (rmu0e != rmu0) e0 = exp(-taup * rmu0);
+  }
   out.put(RL::Tau + 1, beam ? e0 : 1.0);
   if (!isfinite(chk + taup)) st |= kStNonFinite;
   return st;

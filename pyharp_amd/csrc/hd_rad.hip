@@ -446,9 +446,9 @@ HD_RUNROLL
 HD_RUNROLL
       for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
       double den = fma(-kk[j], kk[j], r2);
-      if (fabs(den) < 1.0e-9 * r2) {
+      if (fabs(den) < kResClamp * r2) {
         st |= kStResonance;
-        den = den < 0.0 ? -1.0e-9 * r2 : 1.0e-9 * r2;
+        den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
       }
       tt[j] = t / den;
     }

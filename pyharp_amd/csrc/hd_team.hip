@@ -146,6 +146,7 @@ __global__ __launch_bounds__(kTeamBlock) void hd_team_layer_kernel(LayerArgs A) 
     team_usolve<NN>(lt, rdl, lxd);
   }
   double cvec = 0.0, db = 0.0, bsum = 0.0;
+  bool thin = false;  // 0 < tau' < kThinTau under a Planck source (hd_device.hpp)
   if (A.planck) {
     const double bt = A.planckv[(size_t)(L - lc) * A.nsc + sl];
     // a transparent layer carries its top level's Planck value through
@@ -154,10 +155,12 @@ __global__ __launch_bounds__(kTeamBlock) void hd_team_layer_kernel(LayerArgs A) 
     db = bb - bt;
     bsum = bt + bb;
     const double b1 = taup > 0.0 ? 2.0 * db / taup : 0.0;
+    thin = taup > 0.0 && taup < kThinTau;
     cvec = sd_i * mu_i;
     team_lsolve<NN>(lch, rdl, cvec);
     team_usolve<NN>(lt, rdl, cvec);
-    cvec = fma(b1 * rg_i, cvec, db) * msk;
+    // a thin layer keeps the slope part 2 (dB/tau') h alone here: Q~- takes it below
+    cvec = fma(b1 * rg_i, cvec, thin ? 0.0 : db) * msk;
   }
 
   // ---- eigenpairs (c_soleig): Sym = L^T (-A+) L = V diag(k^2) V^T ----
@@ -223,14 +226,32 @@ __global__ __launch_bounds__(kTeamBlock) void hd_team_layer_kernel(LayerArgs A) 
     team_umsolve<NN>(lt, rdl, pst);  // Psi^T rows = L^-T V Gamma^1/2
     // ---- beam particular solution Z+/- (c_upbeam) ----
     double tt = 0.0;  // lane j: (V^T y2)_j / (1/mu0^2 - k_j^2)
+    double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
     if (beam) {
       const double r2 = rmu0 * rmu0;
       double t = 0.0;
       sfor<0, NN>([&](auto K) { t = fma(vt[HD_K(K)], bc<HD_K(K)>(y2), t); });
       double den = fma(-kk, kk, r2);
-      if (act && fabs(den) < 1.0e-9 * r2) {
-        st |= kStResonance;
-        den = den < 0.0 ? -1.0e-9 * r2 : 1.0e-9 * r2;
+      const bool res = act && fabs(den) < kResMove * r2;
+      if (__any(res)) {
+        // the team's lane nearest the resonance hands 1/mu0'^2 to its team (0: no resonance
+        // in this team; a second eigenvalue within kResMove of it would keep a small
+        // denominator: not known to occur, and kStNonFinite would report it)
+        const double cand =
+            res ? kk * kk * (den < 0.0 ? 1.0 - kResMove : 1.0 + kResMove) : 0.0;
+        const double dist = res ? fabs(den) : 2.0 * r2;
+        double r2e = 0.0, dmin = 2.0 * r2;
+        sfor<0, NN>([&](auto K) {
+          const double c = bc<HD_K(K)>(cand);
+          const double dk = bc<HD_K(K)>(dist);
+          r2e = dk < dmin ? c : r2e;
+          dmin = dk < dmin ? dk : dmin;
+        });
+        if (r2e != 0.0) {
+          st |= kStResonance;
+          rmu0e = sqrt(r2e);
+          den = fma(-kk, kk, r2e);
+        }
       }
       tt = t / den * msk;
     }
@@ -249,16 +270,31 @@ __global__ __launch_bounds__(kTeamBlock) void hd_team_layer_kernel(LayerArgs A) 
       // tauc null: sources for a unit beam at the layer top (the sweep scales them)
       const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
       const double att = 0.5 * exp(-tauc * rmu0);
-      const double dd = rg_i * fma(-yy, rmu0, lxd);
+      const double dd = rg_i * fma(-yy, rmu0e, lxd);
       zp = (sv + dd) * att;
       zm = (sv - dd) * att;
-      e0 = exp(-taup * rmu0);
+      e0 = exp(-taup * rmu0e);
     }
     // ---- layer operators in the flux-weighted basis: Omega rows ----
     sfor<0, NN>([&](auto J) { omr[HD_K(J)] = u[HD_K(J)] * bc<HD_K(J)>(dsq); });
   }
-  const double ga = g_i * (cvec - fma(-zp, e0, zm));
+  double ga = g_i * (cvec - fma(-zp, e0, zm));
   const double gb = g_i * (fma(zp, e0, zm) + bsum);
+  // Thin thermal layer: x = g (2 dB/tau') h is O(dB / tau') and Q~- = I - A- is O(tau'),
+  // a difference of O(1) numbers.  Q~- = A- Omega Omega^T has no such difference: with
+  // w = Omega Omega^T x (O(dB)) and ga0 = g (dB - a) the rest,
+  // Q~- (ga0 + x) = ga0 - A- (ga0 - w): ga carries ga0 - w, pv starts from ga0.
+  double ga0 = ga;
+  if (thin) {
+    const double x = g_i * cvec;
+    double w = 0.0;
+    sfor<0, NN>([&](auto J) {  // y_j = sum_i Omega_ij x_i (over the team's lanes)
+      const double yj = bc<0>(team_sum(omr[HD_K(J)] * x));
+      w = fma(omr[HD_K(J)], yj, w);
+    });
+    ga0 = g_i * (db - fma(-zp, e0, zm));
+    ga = ga0 - w;
+  }
   // By Woodbury, Q~- = I - A- and Q~+ = A+ - I with A- = (I + Omega Omega^T)^-1,
   // A+ = (I + Psi^T Psi)^-1 (SPD, eigenvalues in (0, 1]); lane i gets row i of
   // each inverse from the Cholesky rows J by two lane-local triangular solves
@@ -306,7 +342,7 @@ __global__ __launch_bounds__(kTeamBlock) void hd_team_layer_kernel(LayerArgs A) 
     });
     spd_inverse_row(hp, ap_);
   }
-  double pv = ga, qv = -gb;  // Q~- ga = ga - A- ga,  Q~+ gb = A+ gb - gb
+  double pv = ga0, qv = -gb;  // Q~- ga = ga - A- ga,  Q~+ gb = A+ gb - gb
   sfor<0, NN>([&](auto J) {
     constexpr int j = HD_K(J);
     pv = fma(-am_[j], bc<j>(ga), pv);

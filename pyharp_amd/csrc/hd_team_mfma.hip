@@ -348,6 +348,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     team_usolve<NN>(lt, rdl, lxd);
   }
   double cvec = 0.0, db = 0.0, bsum = 0.0;
+  bool thin = false;  // 0 < tau' < kThinTau under a Planck source (hd_device.hpp)
   if (A.planck) {
     const double bt = A.planckv[(size_t)(L - lc) * A.nsc + sl];
     // a transparent layer carries its top level's Planck value through
@@ -356,10 +357,12 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     db = bb - bt;
     bsum = bt + bb;
     const double b1 = taup > 0.0 ? 2.0 * db / taup : 0.0;
+    thin = taup > 0.0 && taup < kThinTau;
     cvec = sd_i * mu_i;
     team_lsolve<NN>(lch, rdl, cvec);
     team_usolve<NN>(lt, rdl, cvec);
-    cvec = fma(b1 * rg_i, cvec, db) * msk;
+    // a thin layer keeps the slope part 2 (dB/tau') h alone here: Q~- takes it below
+    cvec = fma(b1 * rg_i, cvec, thin ? 0.0 : db) * msk;
   }
   {
     double z[NN];
@@ -443,6 +446,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
   // LDS holds what the next phase reads: S0 = L^-T rows, then W; S1 = C^-T rows,
   // then B^T rows, then U^T (whose rows and columns feed the two beam matvecs)
   double zp = 0.0, zm = 0.0, e0 = 0.0;
+  double wth = 0.0;  // thin thermal layer: Omega Omega^T (g x slope part), see ga below
   {
     double X[4][4], Y[4][4], U[4][4], UT[4][4];
     get_mt(S0, h, c, X);          // L^-1 (M)
@@ -466,9 +470,34 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
       const double r2 = rmu0 * rmu0;
       const double tv = team_matvec<NN>(r_, w2);
       double den = fma(-kk, kk, r2);
-      if (act && fabs(den) < 1.0e-9 * r2) {
-        st |= kStResonance;
-        den = den < 0.0 ? -1.0e-9 * r2 : 1.0e-9 * r2;
+      double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
+      if constexpr (SPHER) {
+        if (act && fabs(den) < kResClamp * r2) {
+          st |= kStResonance;
+          den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
+        }
+      } else {
+        const bool res = act && fabs(den) < kResMove * r2;
+        if (__any(res)) {
+          // the team's lane nearest the resonance hands 1/mu0'^2 to its team (0: no resonance
+          // in this team; a second eigenvalue within kResMove of it would keep a small
+          // denominator: not known to occur, and kStNonFinite would report it)
+          const double cand =
+              res ? kk * kk * (den < 0.0 ? 1.0 - kResMove : 1.0 + kResMove) : 0.0;
+          const double dist = res ? fabs(den) : 2.0 * r2;
+          double r2e = 0.0, dmin = 2.0 * r2;
+          sfor<0, NN>([&](auto K) {
+            const double cv = bc<HD_K(K)>(cand);
+            const double dk = bc<HD_K(K)>(dist);
+            r2e = dk < dmin ? cv : r2e;
+            dmin = dk < dmin ? dk : dmin;
+          });
+          if (r2e != 0.0) {
+            st |= kStResonance;
+            rmu0e = sqrt(r2e);
+            den = fma(-kk, kk, r2e);
+          }
+        }
       }
       const double ttv = tv / den * msk;
       get_cols<NN>(S1, t, i, r_);
@@ -484,7 +513,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
         const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
         att = 0.5 * exp(-tauc * rmu0);
       }
-      const double dd = rg_i * fma(-yy, rmu0, lxd);
+      const double dd = rg_i * fma(-yy, rmu0e, lxd);
       zp = (sv + dd) * att;
       zm = (sv - dd) * att;
       if constexpr (SPHER) {  // a layer of zero depth leaves the diffuse field alone
@@ -492,8 +521,16 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
                               P->chp[(size_t)(lc + 1) * A.nsc + sl])
                         : 1.0;
       } else {
-        e0 = exp(-taup * rmu0);
+        e0 = exp(-taup * rmu0e);
       }
+    }
+    if (thin) {  // w = U Delta U^T x from the rows and columns of U^T in S1
+      double r_[NN];
+      const double dq = G[t * 32 + i];  // Delta_i^1/2, this lane's own
+      get_rows<NN>(S1, t, i, r_);
+      const double yv = team_matvec<NN>(r_, g_i * cvec) * dq;
+      get_cols<NN>(S1, t, i, r_);
+      wth = team_matvec<NN>(r_, yv * dq) * msk;
     }
     get_m(S0, h, c, Y);            // W (M)
     mprod<false>(U, Y, X, h, c);   // U^T W
@@ -512,7 +549,12 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     put_m(S1, h, c, Y);
     lds_fence();
   }
-  const double ga = g_i * (cvec - fma(-zp, e0, zm));
+  // Thin thermal layer: x = g (2 dB/tau') h is O(dB / tau') and Q~- = I - A- is O(tau'),
+  // a difference of O(1) numbers.  Q~- = A- Omega Omega^T has no such difference: with
+  // w = Omega Omega^T x (O(dB)) and ga0 = g (dB - a) the rest,
+  // Q~- (ga0 + x) = ga0 - A- (ga0 - w): ga carries ga0 - w, pv starts from ga0.
+  const double ga0 = g_i * ((thin ? db : cvec) - fma(-zp, e0, zm));
+  const double ga = ga0 - wth;
   const double gb = g_i * (fma(zp, e0, zm) + bsum);
 
   // ---- A- = (I + Omega Omega^T)^-1, A+ = (I + Psi^T Psi)^-1 ----
@@ -534,7 +576,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     put_m(S0, h, c, Am);
     lds_fence();
     get_rows<NN>(S0, t, i, hr);
-    pv = ga - team_matvec<NN>(hr, ga);
+    pv = ga0 - team_matvec<NN>(hr, ga);
     get_rows<NN>(S1, t, i, hr);
     if (!team_chol<NN, false>(hr, unused, jrd)) st |= kStEigen;
     team_tri_inverse_col<NN>(hr, jrd, z);  // row i of K+^T
@@ -1531,9 +1573,9 @@ __global__ __launch_bounds__(64, 2) void hd_rad_team_layer_kernel(RadArgs A) {
       const double r2 = rmu0 * rmu0;
       const double tv = team_matvec<NN>(r_, w2);
       double den = fma(-kk, kk, r2);
-      if (act && fabs(den) < 1.0e-9 * r2) {
+      if (act && fabs(den) < kResClamp * r2) {
         st |= kStResonance;
-        den = den < 0.0 ? -1.0e-9 * r2 : 1.0e-9 * r2;
+        den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
       }
       const double ttv = tv / den * msk;
       get_cols<NN>(S1, t, i, r_);

@@ -26,6 +26,25 @@ import numpy as np
 
 from oracle.disort_np import DITHER, double_gauss, legendre_table, plkavg
 
+# The two cold branches of the flux layer kernels, with the
+# kernels' constants (hd_device.hpp kResMove / kThinTau); scripts/hard_threshold_sweep.py
+# sweeps both against the mp reference.
+#
+# RES_MOVE: where |1/mu0^2 - k_j^2| < RES_MOVE / mu0^2 for a mode j of the layer, the layer
+# is solved for the secant 1/mu0'^2 = k_j^2 (1 +- RES_MOVE) (the side mu0 is on) wherever
+# the resonant mode's amplitude goes: the denominators, the difference part of the
+# particular solution and the beam's attenuation inside the layer.  RES_CLAMP is the
+# earlier rule (the one denominator clamped at +-1e-9 / mu0^2, nothing else moved), kept
+# for the sweep: it drops that mode's share of the beam source.
+RES_MOVE = 3.0e-8
+RES_CLAMP = None
+# THIN_TAU: in a layer of scaled depth 0 < tau' < THIN_TAU the slope part of the thermal
+# source, x = g 2 (dB / tau') h, goes through Q~- = A- Omega Omega^T (products only)
+# instead of Q~- = I - A- (a difference of O(1) numbers for an O(tau') result, which under
+# dB / tau' leaves an error eps dB / tau').  0: the difference form everywhere, the
+# earlier rule.  tau' = 0 carries the top level's value through, as before.
+THIN_TAU = 1.0e-3
+
 
 def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
     nn = nstr // 2
@@ -84,28 +103,46 @@ def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
     zm = np.zeros(nn)
     e0 = 1.0
     if fbeam > 0 and umu0 > 0:
-        e0 = math.exp(-taup / umu0)
+        r2 = 1.0 / umu0 ** 2
+        den = r2 - k2
+        rmu0 = 1.0 / umu0
+        if RES_CLAMP is not None:
+            small = np.abs(den) < RES_CLAMP * r2
+            den = np.where(small, np.where(den < 0.0, -RES_CLAMP * r2, RES_CLAMP * r2), den)
+        else:
+            j = int(np.argmin(np.abs(r2 - k2)))  # the mode nearest the resonance
+            if abs(r2 - k2[j]) < RES_MOVE * r2:
+                r2m = k2[j] * (1.0 - RES_MOVE if r2 < k2[j] else 1.0 + RES_MOVE)
+                rmu0 = math.sqrt(r2m)
+                den = r2m - k2
+        e0 = math.exp(-taup * rmu0)
         p0 = legendre_table(nstr, [umu0])[:, 0]
         xs = fbeam / (2 * math.pi) * (pt[ev].T @ (gl[ev] * p0[ev]))
         xd = -fbeam / (2 * math.pi) * (pt[~ev].T @ (gl[~ev] * p0[~ev]))
         rv = -(1.0 / (mu * sd)) * (lch @ (lch.T @ (sd * xs))) + xd / (mu * umu0)
         ttv = u.T @ np.linalg.solve(lch.T, np.linalg.solve(lch, (w / sd) * rv))   # V^T y2 = U^T L^-T y2
-        ttv = ttv / (1.0 / umu0 ** 2 - k2)
+        ttv = ttv / den
         svec = (sd / w) * (u @ ttv)           # X tt, X = W^-1 D^1/2 L V = W^-1 D^1/2 U
-        dd = linv(xd - mu * svec / umu0)
+        dd = linv(xd - mu * svec * rmu0)
         att = math.exp(-tauc_top / umu0)
         zp = 0.5 * (svec + dd) * att
         zm = 0.5 * (svec - dd) * att
+    if not taup > 0.0:
+        b_bot = b_top
     db = b_bot - b_top
     bsum = b_top + b_bot
+    thin = 0.0 < taup < THIN_TAU
+    cslope = np.zeros(nn)
     if b_top != 0.0 or b_bot != 0.0:
         b1 = db / taup if taup > 0 else 0.0
-        cvec = db + 2.0 * b1 * linv(mu)
-    else:
-        cvec = np.zeros(nn)
+        cslope = 2.0 * b1 * linv(mu)
     avec = zm - zp * e0
     bvec = zm + zp * e0
-    pv = qtm @ (g * (cvec - avec))
+    if thin:
+        # Q~- = I - A- = A- Omega Omega^T: no difference of O(1) numbers under dB / tau'
+        pv = qtm @ (g * (db - avec)) + aminus @ (omega @ (omega.T @ (g * cslope)))
+    else:
+        pv = qtm @ (g * (db + cslope - avec))
     qv = qtp @ (g * (bvec + bsum))
     splus_src = g * (zp * (1 - e0) - db) + pv - qv
     sminus_src = g * (-zm * (1 - e0) + db) - pv - qv
@@ -118,8 +155,8 @@ def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
 
 
 def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
-                 fisot=0.0, planck=False, temper=None, btemp=0.0, wvnmlo=0.0,
-                 wvnmhi=0.0):
+                 fisot=0.0, planck=False, temper=None, btemp=0.0, ttemp=0.0, temis=0.0,
+                 wvnmlo=0.0, wvnmhi=0.0):
     """Layers top->bottom; returns (flup, fdn) at nlyr+1 levels top->bottom."""
     nn = nstr // 2
     mu, w = double_gauss(nn)
@@ -136,7 +173,7 @@ def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
         ops.append(o)
     c = 2 * math.pi * w * mu
     ra = np.zeros((nn, nn))
-    sd = np.full(nn, fisot)
+    sd = np.full(nn, fisot + (temis * plkavg(wvnmlo, wvnmhi, ttemp) if planck else 0.0))
     store = []
     for o in ops:
         w1 = np.eye(nn) - o["r"] @ ra

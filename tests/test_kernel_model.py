@@ -88,3 +88,64 @@ def test_radiance_model_matches_oracle(seed):
                                    albedo=alb, fisot=fisot, bsurf=bsurf, btop=btop)
             err = np.abs(got - ref[:, iu]).max() / scale
             assert err < 1e-9, (m, mu, got, ref[:, iu])
+
+
+# --------------------------------------------------------------------------- #
+# the hard-regime fixture (tests/hard_cases.py, mp reference): where a formulation
+# defect of the kernels shows without a GPU
+# --------------------------------------------------------------------------- #
+@pytest.fixture(scope="module")
+def hard_fixture():
+    import hard_cases
+    from helpers import GOLDEN
+    return hard_cases.load(GOLDEN)
+
+
+def _model_batch(b):
+    """The model's (1, C, L+1, 2) fluxes of a fixture batch, harp layout."""
+    import hard_cases
+    nlyr, nstr = b["nlyr"], b["nstr"]
+    out = np.zeros((1, b["prop"].shape[1], nlyr + 1, 2))
+    for c in range(out.shape[1]):
+        p = b["prop"][0, c, ::-1]
+        kw = {k: float(v[0, c]) for k, v in b["bc"].items()}
+        if b["planck"]:
+            kw.update(planck=True, temper=b["temf"][c, ::-1], wvnmlo=hard_cases.WAVE[0],
+                      wvnmhi=hard_cases.WAVE[1])
+        fu, fd = solve_column(p[:, 0], p[:, 1], [list(r[2:2 + b["nmom"]]) for r in p], nstr, **kw)
+        out[0, c, :, 0], out[0, c, :, 1] = fu[::-1], fd[::-1]
+    return out
+
+
+@pytest.mark.parametrize("nstr", [2, 4, 8, 16])
+@pytest.mark.parametrize("family", ["phase", "conservative", "depth", "thin_thermal",
+                                    "resonance"])
+def test_model_on_hard_fixture(hard_fixture, family, nstr):
+    """Every fixture column with nstr <= 16 at TOL against the mp reference."""
+    from helpers import TOL, rel_err
+    from oracle.disort_mp import flux_of_record
+    worst = 0.0
+    for b in hard_fixture[family, nstr]:
+        err = rel_err(_model_batch(b), flux_of_record(b["ref"])).max(axis=(0, 2, 3))
+        print(f"  {family} n{nstr} {b['name']}: worst {err.max():.3e} (column {err.argmax()})")
+        worst = max(worst, err.max())
+    assert worst < TOL
+
+
+def test_model_shows_what_the_two_rules_replace(hard_fixture):
+    """With the earlier rules (one denominator clamped at 1e-9 / mu0^2, dB / tau' formed at
+    any tau' > 0) the same columns miss TOL by orders of magnitude: the fixture sees both."""
+    import kernel_model
+    from helpers import TOL, rel_err
+    from oracle.disort_mp import flux_of_record
+    saved = kernel_model.RES_CLAMP, kernel_model.THIN_TAU
+    try:
+        kernel_model.RES_CLAMP, kernel_model.THIN_TAU = 1.0e-9, 0.0
+        res = [b for b in hard_fixture["resonance", 8] if b["name"] == "scat"][0]
+        thin = [b for b in hard_fixture["thin_thermal", 8] if b["name"] == "top2"][0]
+        e_res = rel_err(_model_batch(res), flux_of_record(res["ref"])).max()
+        e_thin = rel_err(_model_batch(thin), flux_of_record(thin["ref"])).max()
+    finally:
+        kernel_model.RES_CLAMP, kernel_model.THIN_TAU = saved
+    print(f"  clamp: {e_res:.3e}   dB/tau': {e_thin:.3e}")
+    assert e_res > 1e3 * TOL and e_thin > 1e3 * TOL

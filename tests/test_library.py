@@ -258,6 +258,7 @@ def test_product_never_imports_oracle():
                     src = f.read()
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, re.M), fn
                 assert "hdoracle" not in src, fn
+                assert not re.search(r"^\s*(from|import)\s+mpmath", src, re.M), fn
 
 
 def test_scattering_moments():
