@@ -110,7 +110,7 @@ def load(path: str = LIB_PATH):
     """Load libhdisort.so; raises OSError if it has not been built.
 
     HD_LIB_PATH overrides the path (A/B runs of kernel variants built
-    out of tree by mb/build_variant.sh)."""
+    out of tree by scripts/ab/build_variant.sh or scripts/ab/kvariant.sh)."""
     global _lib
     if _lib is not None:
         return _lib

@@ -48,21 +48,9 @@ struct hd_context {
   // team-path Jacobi from the tabulated (ssa, chi_1) eigenvectors
   // (hd_kernels.hpp); HD_JACOBI_WARM=0 in the environment turns it off (A/B)
   int warm = 1;
-  // team path: the two-waves-per-SIMD sweep (hd_team_mfma_sweep_lean_kernel, the
-  // default); HD_TEAM_SWEEP_LEAN=0 in the environment picks the one-wave sweep when
-  // a context is created
-  int lean = 1;
   // nstr 4 / 8: the sweep in NN-lane teams (hd_sweep_quad_kernel) for chunks of at
   // most kQuadMaxSolves solves (-1, the default), always (1) or never (0): HD_SWEEP_QUAD
   int quad = -1;
-  // nstr 16: the adding sweep with the stack state in LDS (hd_sweep_lean_kernel,
-  // two waves per SIMD) -- off by default: 1 024 waves per chunk spread one per SIMD
-  // and each runs 1.85 ms against hd_sweep_kernel's 1.4 (C4 12.38 vs 12.77 M,
-  // profiles/r05/lean8_ab.txt); HD_AB=1 HD_SWEEP_LEAN8=1 picks it
-  int lean8 = 0;
-  // nstr 16: layer setup, adding sweep and back-substitution of a chunk in one kernel
-  // (hd_column_kernel: no layer records in HBM); HD_AB=1 HD_COLUMN=0|1
-  int column = 0;
   // true while a solve enqueues into a capturing stream: scratch may not grow then
   bool capturing = false;
   std::string err;
@@ -229,7 +217,7 @@ using hd::max_auto_chunk;
 // hd_solve_band's row-major route (hd_plan.hpp: band_rowmajor_size) under the context's
 // switches
 bool band_rowmajor(const hd_context* ctx, int nn, long nsolve) {
-  return ctx->chunk <= 0 && !ctx->band_cmaj && !ctx->column && hd::band_rowmajor_size(nn, nsolve);
+  return ctx->chunk <= 0 && !ctx->band_cmaj && hd::band_rowmajor_size(nn, nsolve);
 }
 
 // the last solve that used the context's buffers has finished (before a free)
@@ -422,11 +410,6 @@ int hd_context_create(hd_context** out, int device) {
   if (const char* e = hd::ab_env("HD_JACOBI_WARM")) ctx->warm = std::atoi(e) != 0;
   if (const char* e = hd::ab_env("HD_SWEEP_QUAD")) ctx->quad = std::atoi(e) < 0 ? -1 : std::atoi(e) != 0;
   if (const char* e = hd::ab_env("HD_BAND_CMAJ")) ctx->band_cmaj = std::atoi(e) != 0;
-#if HD_AB_VARIANTS
-  if (const char* e = hd::ab_env("HD_TEAM_SWEEP_LEAN")) ctx->lean = std::atoi(e) != 0;
-  if (const char* e = hd::ab_env("HD_SWEEP_LEAN8")) ctx->lean8 = std::atoi(e) != 0;
-  if (const char* e = hd::ab_env("HD_COLUMN")) ctx->column = std::atoi(e) != 0;
-#endif
   ctx->device = device;
   auto init = [ctx]() -> int {
     HD_HIP(ctx, hipSetDevice(ctx->device));
@@ -644,7 +627,7 @@ hipError_t timed(hipEvent_t* ev, int i, hipStream_t st, Launch&& launch) {
 // One call's shared setup: what the pipelines below (one function per path) launch from.
 // flx (hd_solve_flx; flux and band null): the same chunks and streams with the flx
 // instantiations -- register path hd_layer_kernel -> hd_sweep_flx_kernel ->
-// hd_backsub_flx_kernel / _tail_kernel (never the NN-lane, LDS-state or column sweeps),
+// hd_backsub_flx_kernel / _tail_kernel (never the NN-lane sweep),
 // team path hd_team_mfma_layer_kernel -> hd_team_mfma_sweep_flx_kernel -- over the wider
 // back-substitution records, plus the per-level prologue hd_flx_level_kernel, whose
 // output only the sweep (surface level) and the back-substitution read.
@@ -729,9 +712,7 @@ struct SolveCall {
     sa.cmaj = cmaj;
     sa.nwave = in->nwave;
     sa.beam_scale = beam_in_sweep ? 1 : 0;
-    sa.lean = ctx->lean;
     sa.quad = ctx->quad;
-    sa.lean8 = ctx->lean8;
     if (band && reg) {
       sa.wts = band->weight;
       sa.part = at(hd::kRPart, 0);
@@ -885,27 +866,6 @@ int solve_one_chunk(const SolveCall& c) {
   return e == hipSuccess ? HD_OK : c.launch_failed(e);
 }
 
-// nstr 16 by the column kernel (A/B build): every chunk wholly on the caller's stream
-int solve_column(const SolveCall& c) {
-  long k = 0;
-  for (long s0 = 0; s0 < c.nsolve; s0 += c.chunk, ++k) {
-    const int nsc = c.nsc_at(s0), buf = (int)(k & 1);
-    int rc = c.prologue(s0, nsc, buf, c.stream);
-    if (rc) return rc;
-    const hd::LayerArgs la = c.layer_args(s0, nsc, buf);
-    const hd::SweepArgs sa = c.sweep_args(s0, nsc, buf);
-    hipEvent_t* ev;
-    rc = timing_quad(c.ctx, &ev);
-    if (rc) return rc;
-    hipError_t e =
-        timed(ev, 0, c.stream, [&] { return hd::launch_column_nn(c.nn, la, sa, c.stream); });
-    if (e == hipSuccess) e = timed(ev, 2, c.stream, [] { return hipSuccess; });
-    if (e == hipSuccess && c.band) e = hd::launch_band_reduce(c.band_args(s0, nsc, buf), c.stream);
-    if (e != hipSuccess) return c.launch_failed(e);
-  }
-  return HD_OK;
-}
-
 // Register path (three streams): chunk k uses buffer k&1; its layer kernel
 // (stream lay) runs beside chunk k-1's sweep (the caller's stream), its
 // back-substitution (side stream) beside chunk k+1's layer kernel, and chunk
@@ -1048,7 +1008,6 @@ int solve_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, do
   c.status = status;
   HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
   HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
-  if (reg && nn == 8 && ctx->column && !flx && !sph) return solve_column(c);
   if (nsolve <= chunk) return solve_one_chunk(c);
   return reg ? solve_reg_pipeline(c) : solve_team_pipeline(c);
 }

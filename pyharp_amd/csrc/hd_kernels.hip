@@ -64,16 +64,6 @@ __device__ __forceinline__ const Quad<NN>& quad() {
   else if constexpr (NN == 7) return c_quad.q7;
   else return c_quad.q8;
 }
-// the same table through a pointer the compiler cannot see through: inside a
-// loop, products of table entries are then formed where used instead of being
-// hoisted out of the loop and held (the column kernel's layer loop spilled 60 of
-// them), and the entries come back by scalar loads
-template <int NN>
-__device__ __forceinline__ const Quad<NN>& quad_opaque() {
-  const Quad<NN>* p = &quad<NN>();
-  asm volatile("" : "+s"(p));
-  return *p;
-}
 
 // one wave per block: a layer-kernel wave can take any SIMD the previous chunk's
 // sweep leaves free (hd_solve runs the two on separate streams)
@@ -297,50 +287,21 @@ __host__ __device__ constexpr int psi_doubles() {
   return NN > 1 ? (NN == 2 ? 5 : NN * NN) : 1;
 }
 
-// On-chip layer record of the column kernel: its layer setup writes the RecL
-// elements here and its adding sweep reads them back -- no record in HBM.  R~ and
-// S~+ (used first) stay in registers (compile-time indices after unrolling); T~,
-// S~- and tau' (used after the sweep's LU) go to this lane's Psi^T staging area
-// of LDS, free between the layer setup's last Psi^T read and the next layer's
-// Jacobi, so that they are not live in registers across the LU.
-template <int NN>
-struct ColRec {
-  using RL = RecL<NN>;
-  static constexpr int kSm = even_up(RL::nsym);  // LDS slot of S~-[0]
-  static_assert(kSm + (RL::Tau + 1 - RL::Sm) <= psi_doubles<NN>() || NN == 1,
-                "T~, S~-, tau' do not fit the Psi^T staging area");
-  double v[RL::T + even_up(NN)];  // R~ | S~+ (at RL::T ..)
-  double* lds;                   // psi_lds + lane
-  __device__ __forceinline__ int slot(int e) const { return e < RL::Sp ? e - RL::T : kSm + (e - RL::Sm); }
-  __device__ __forceinline__ void put(int e, double x) {
-    if (e < RL::T) v[e] = x;
-    else if (e >= RL::Sp && e < RL::Sm) v[RL::T + (e - RL::Sp)] = x;
-    else if (e <= RL::Tau) lds[slot(e) * kLayerBlock] = x;
-  }
-  __device__ __forceinline__ double get(int e) const {
-    if (e < RL::T) return v[e];
-    if (e >= RL::Sp && e < RL::Sm) return v[RL::T + (e - RL::Sp)];
-    return lds[slot(e) * kLayerBlock];
-  }
-  __device__ __forceinline__ void close(int) {}
-};
-
-// The layer setup of (solve s, solver layer lc) into the record sink `out`
-// (PairOut: RecL in HBM; ColRec: on chip).  psi_lds: this wave's Psi^T
-// staging, element e of lane lt at e * kLayerBlock + lt.  Returns the status bits.
-// OPQ: the quadrature table through quad_opaque (the column kernel's layer loop)
+// The layer setup of (solve s, solver layer lc) into its RecL record through `out`.
+// psi_lds: this wave's Psi^T staging, element e of lane lt at e * kLayerBlock + lt.
+// Returns the status bits.
 // SPHER (pseudo-spherical beam): the beam's secant in this layer
 // is hd_spher_kernel's lambda (any sign, or zero) in place of 1/mu0, its amplitude at the
 // layer top exp(-ch'_top) and its transmission exp(-(ch'_bottom - ch'_top)); the phase
 // function keeps the true mu0
-template <int NN, bool OPQ, class Out, bool SPHER = false>
+template <int NN, bool NT, bool SPHER = false>
 __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, int lc,
-                                          double* psi_lds, int lt, Out& out,
+                                          double* psi_lds, int lt, PairOutT<NT>& out,
                                           const double* pf = nullptr, float* pf_sink = nullptr,
                                           const SphArgs* P = nullptr) {
   constexpr int N = 2 * NN;
   constexpr int kPsi = psi_doubles<NN>();
-  const Quad<NN>& Qc = OPQ ? quad_opaque<NN>() : quad<NN>();
+  const Quad<NN>& Qc = quad<NN>();
   const int L = A.nlyr;
   const int nm = A.nmom;
   const int np = A.nprop;
@@ -830,9 +791,10 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   out.close(RL::Sm + NN - 1);
   out.put(RL::Tau, taup);
   // the pad after tau': the layer's direct-beam transmission e^(-tau'/mu0) (1
-  // without a beam), from which hd_sweep_lean_kernel carries the beam down as a
-  // running product instead of an exp of the running depth
-  // (the beam's own transmission, not the one of a secant moved off a resonance)
+  // without a beam; the beam's own transmission, not the one of a secant moved off
+  // a resonance).  No kernel reads it any more -- its one reader was the LDS-state
+  // nstr-16 sweep -- and dropping the store is a change to this
+  // kernel's code, left for a change that is measured
   if constexpr (!SPHER) {
     if (rmu0e != rmu0) e0 = exp(-taup * rmu0);
   }
@@ -882,10 +844,10 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
     }
   }
   const int st =
-      layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink);
+      layer_body<NN, NT>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink);
 #else
   const int st =
-      layer_body<NN, false>(A, s, sl, lc, psi_lds, lt, out);
+      layer_body<NN, NT>(A, s, sl, lc, psi_lds, lt, out);
 #endif
   if (st) {
     atomicOr(&A.status[s], st);
@@ -936,10 +898,10 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_spher_kernel(LayerArgs A
     }
   }
   const int st =
-      layer_body<NN, false, PairOutT<NT>, true>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink, &P);
+      layer_body<NN, NT, true>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink, &P);
 #else
   const int st =
-      layer_body<NN, false, PairOutT<NT>, true>(A, s, sl, lc, psi_lds, lt, out, nullptr, nullptr, &P);
+      layer_body<NN, NT, true>(A, s, sl, lc, psi_lds, lt, out, nullptr, nullptr, &P);
 #endif
   if (st) {
     atomicOr(&A.status[s], st);
@@ -969,10 +931,12 @@ __device__ __forceinline__ void flx_emit(const FlxArgs& F, long s, long sl, size
 }
 
 // The adding sweep of solve s (chunk lane sl): layer lc's record through
-// rec_at(lc), a callable returning a getter e -> RecL element e (hd_sweep_kernel:
-// loads from the HBM record; hd_column_kernel: the layer setup run right there
-// into registers).  Stores the back-substitution records, the surface level and
-// x; returns the status bits.
+// rec_at(lc), a callable returning a getter e -> RecL element e (loads from the
+// HBM record).  Stores the back-substitution records, the surface level and
+// x; returns the status bits.  The three wrappers below pass the same accessor:
+// stated once in here (or as one shared helper) it gave every sweep kernel
+// different instructions and registers, so it stays a parameter until that is
+// measured (profiles/retire/README.md).
 // FLX (hd_solve_flx): the records are RecBF -- each level also gets the mean-intensity
 // row rh and scalar ch -- and the surface level's eight components go to F->flx.
 // SPHER (pseudo-spherical beam): the direct beam at every level is exp(-ch') of
@@ -1340,397 +1304,6 @@ __global__ __launch_bounds__(64) void hd_sweep_flx_kernel(SweepArgs A, FlxArgs F
 template <int NN, bool PRE, bool NT, bool FLX = false>
 __device__ __forceinline__ void backsub_body(const SweepArgs& A, const FlxArgs* F = nullptr);
 
-#if HD_AB_VARIANTS
-// ============================================================================
-// K1+K2+K3 in one pass per solve (the column kernel): one lane walks its solve's
-// layers top -> bottom, runs each layer's setup (layer_body) into registers and
-// feeds it straight to the adding sweep (sweep_body), then walks back up through
-// the back-substitution records it wrote (backsub_body).  The same source
-// arithmetic as hd_layer_kernel + hd_sweep_kernel + the back-substitution (to
-// rounding: the compiler may contract differently in the fused body), but the
-// layer records (RecL: 90 doubles per (solve, layer), written once and read once)
-// never reach HBM, and the three kernels' time-sharing of the SIMDs -- neither
-// the layer kernel nor the sweep leaves room on a SIMD for the other -- becomes
-// one instruction stream per wave.  Measured slower at one wave per SIMD (A/B
-// only, HD_COLUMN; profiles/r05/column_ab.txt).
-// ============================================================================
-template <int NN>
-__global__ __launch_bounds__(64) void hd_column_kernel(LayerArgs LA, SweepArgs A) {
-  __shared__ double psi_lds[psi_doubles<NN>() * kLayerBlock];
-  static_assert(kLayerBlock == 64, "column kernel: one wave per block");
-  const int lt = threadIdx.x;
-  const long sl = (long)blockIdx.x * 64 + lt;
-  if (sl < A.nsc) {
-    const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-    ColRec<NN> r;
-    r.lds = psi_lds + lt;
-    int lst = 0;
-    auto rec_at = [&](int lc) {
-      lst |= layer_body<NN, true>(LA, s, (int)sl, lc, psi_lds, lt, r);
-      return [&r](int e) { return r.get(e); };
-    };
-    const int st = sweep_body<NN, false>(A, sl, s, rec_at) | lst;
-    if (st) {
-      atomicOr(&A.status[s], st);
-      if (st & 0x0F) atomicOr(A.anyerr, 1);
-    }
-  }
-  // the back-substitution reads what this wave wrote (with the band epilogue, lanes
-  // past the chunk read the last solve's records)
-  __syncthreads();
-  backsub_body<NN, true, false>(A);
-}
-
-// ============================================================================
-// K2 for nstr 16 (NN = 8) at two waves per SIMD: the adding sweep of
-// hd_sweep_kernel with the stack state (Ra packed upper, Sd) parked in LDS
-// between its uses instead of in registers, and the layer's R~ / T~ read from
-// the record where they are used.  hd_sweep_kernel holds Ra, R~, T~, W1 and
-// M1/P together (492 VGPRs: one wave per SIMD, VALU busy half the time on its
-// dependency chains); here at most W1 and one symmetric 8 x 8 matrix are live
-// (<= 256 VGPRs), so two sweep waves share a SIMD and fill each other's stalls.
-//   W1 = I - R~ Ra          Ra streamed from LDS, packed pair by pair
-//   t1 = W1^-1 (R~ Sd + S+) pivot-free LU (hd_sweep_kernel's)
-//   u  = Ra t1 + Sd         -> LDS (over Sd)
-//   ZT = W1^-1 T~           column by column, stored
-//   M1 = Ra W1^-1           row by row, upper triangle kept (M1 is symmetric)
-//   Ra <- R~ + T~ (M1 T~)   column by column -> LDS; Sd <- T~ u + S-
-// The level fluxes' row vector rc = 2 pi Ra g of the next level is formed while
-// Ra is written and stored into that level's record.  Records as hd_sweep_kernel
-// (RecL in, RecB out): the back-substitution kernels are shared.
-// ============================================================================
-template <int NN>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2)))
-void hd_sweep_lean_kernel(SweepArgs A) {
-  static_assert(NN % 2 == 0, "even NN: Sd fills whole pairs");
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int kRaP = (nsym + 1) / 2;  // LDS pairs of packed Ra
-  constexpr int kSdP = NN / 2;          // then Sd (or u)
-  __shared__ double2 stk[kRaP + kSdP][64];
-  const Quad<NN>& Qc = quad<NN>();
-  const int lt = (int)threadIdx.x;
-  const long sl = (long)blockIdx.x * blockDim.x + lt;
-  if (sl >= A.nsc) return;  // one wave per block: no barrier below
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-  const int L = A.nlyr;
-  const size_t nsc = A.nsc;
-  using RL = RecL<NN>;
-  using RB = RecB<NN>;
-  int st = 0;
-
-  const double twopi = 2.0 * kPi;
-  double f0mu0;
-  {
-    const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
-    const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-    f0mu0 = fb > 0.0 && mu0 > 0.0 ? fb * mu0 : 0.0;
-  }
-
-  // packed element e of Ra / element i of Sd in this lane's LDS slots
-  auto ra_at = [&](int e) {
-    const double2 q = stk[e >> 1][lt];
-    return (e & 1) ? q.y : q.x;
-  };
-  auto sd_load = [&](double (&v)[NN]) {
-#pragma unroll
-    for (int p = 0; p < kSdP; ++p) {
-      const double2 q = stk[kRaP + p][lt];
-      v[2 * p] = q.x;
-      v[2 * p + 1] = q.y;
-    }
-  };
-  auto sd_store = [&](const double (&v)[NN]) {
-#pragma unroll
-    for (int p = 0; p < kSdP; ++p) stk[kRaP + p][lt] = make_double2(v[2 * p], v[2 * p + 1]);
-  };
-  {
-    double top = A.fisot ? A.fisot[s] : 0.0;
-    if (A.planck) top += A.planckv[(size_t)(L + 2) * nsc + sl];
-    double sd0[NN];
-#pragma unroll
-    for (int i = 0; i < NN; ++i) sd0[i] = Qc.g[i] * top;
-#pragma unroll
-    for (int p = 0; p < kRaP; ++p) stk[p][lt] = make_double2(0.0, 0.0);
-    sd_store(sd0);
-    // level 0 (top): Ra = 0, so rc = 0 and cs = g . Sd
-    PairOut bp{reinterpret_cast<double2*>(A.bsub) + sl, nsc, 0.0};
-    double cs = 0.0;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) {
-      bp.put(RB::Rc + i, 0.0);
-      cs = fma(Qc.g[i], sd0[i], cs);
-    }
-    bp.close(RB::Rc + NN - 1);
-    bp.put(RB::Cs, fma(twopi, cs, f0mu0));
-    bp.close(RB::Cs);
-  }
-  double eb = 1.0;  // direct beam at the layer top: running product of transmissions
-
-  for (int lc = 0; lc < L; ++lc) {
-    const double2* lp = reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RL::pairs * nsc + sl;
-    auto rec = [&](int e) { return pair_get(lp, nsc, e); };
-    PairOut bp{reinterpret_cast<double2*>(A.bsub) + (size_t)lc * RB::pairs * nsc + sl, nsc, 0.0};
-    const double sscale = A.beam_scale ? eb : 1.0;
-
-    // ---- W1 = I - R Ra ; v1 = R Sd + S+  (each packed element of Ra once, in
-    //      increasing k for every W1[i][j]: hd_sweep_kernel's fma order) ----
-    double w1[NN][NN], t1[NN];
-    {
-      double rl[NN][NN];  // R~ upper
-      {
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < NN; ++i)
-#pragma unroll
-          for (int j = i; j < NN; ++j) rl[i][j] = rec(RL::R + (e++));
-      }
-#pragma unroll
-      for (int i = 0; i < NN; ++i)
-#pragma unroll
-        for (int j = 0; j < NN; ++j) w1[i][j] = (i == j) ? 1.0 : 0.0;
-      int e = 0;
-#pragma unroll
-      for (int a = 0; a < NN; ++a)
-#pragma unroll
-        for (int b = a; b < NN; ++b, ++e) {
-          const double x = ra_at(e);  // Ra[a][b] = Ra[b][a]
-#pragma unroll
-          for (int i = 0; i < NN; ++i) {
-            w1[i][b] = fma(-HD_SYM(rl, i, a), x, w1[i][b]);
-            if (a != b) w1[i][a] = fma(-HD_SYM(rl, i, b), x, w1[i][a]);
-          }
-        }
-      double sd[NN];
-      sd_load(sd);
-#pragma unroll
-      for (int i = 0; i < NN; ++i) {
-        double t = rec(RL::Sp + i) * sscale;
-#pragma unroll
-        for (int k = 0; k < NN; ++k) t = fma(HD_SYM(rl, i, k), sd[k], t);
-        t1[i] = t;
-      }
-    }
-    HD_PHASE();
-    // LU without pivoting, reciprocal pivots on the diagonal (hd_sweep_kernel's)
-#pragma unroll
-    for (int k = 0; k < NN; ++k) {
-      const double piv = w1[k][k];
-      if (!(fabs(piv) > 1.0e-12)) st |= kStPivot;
-      const double rp = rcp_nr(piv);
-      w1[k][k] = rp;
-#pragma unroll
-      for (int i = k + 1; i < NN; ++i) {
-        const double l = w1[i][k] * rp;
-        w1[i][k] = l;
-#pragma unroll
-        for (int j = k + 1; j < NN; ++j) w1[i][j] = fma(-l, w1[k][j], w1[i][j]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NN; ++i)
-#pragma unroll
-      for (int k = 0; k < i; ++k) t1[i] = fma(-w1[i][k], t1[k], t1[i]);
-#pragma unroll
-    for (int i = NN - 1; i >= 0; --i) {
-#pragma unroll
-      for (int k = i + 1; k < NN; ++k) t1[i] = fma(-w1[i][k], t1[k], t1[i]);
-      t1[i] *= w1[i][i];
-    }
-#pragma unroll
-    for (int i = 0; i < NN; ++i) bp.put(RB::Tv + i, t1[i]);
-    bp.close(RB::Tv + NN - 1);
-    // u = Ra t1 + Sd -> LDS (Sd is not needed again)
-    {
-      double u[NN];
-      sd_load(u);
-      int e = 0;
-#pragma unroll
-      for (int a = 0; a < NN; ++a)
-#pragma unroll
-        for (int b = a; b < NN; ++b, ++e) {
-          const double x = ra_at(e);
-          u[a] = fma(x, t1[b], u[a]);
-          if (a != b) u[b] = fma(x, t1[a], u[b]);
-        }
-      sd_store(u);
-    }
-    HD_PHASE();
-    // ---- ZT = W1^-1 T~ column by column (stored) ----
-    {
-      double tl[NN][NN];
-      {
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < NN; ++i)
-#pragma unroll
-          for (int j = i; j < NN; ++j) tl[i][j] = rec(RL::T + (e++));
-      }
-#pragma unroll
-      for (int j = 0; j < NN; ++j) {
-        double x[NN];
-#pragma unroll
-        for (int i = 0; i < NN; ++i) x[i] = HD_SYM(tl, i, j);
-#pragma unroll
-        for (int i = 0; i < NN; ++i)
-#pragma unroll
-          for (int k = 0; k < i; ++k) x[i] = fma(-w1[i][k], x[k], x[i]);
-#pragma unroll
-        for (int i = NN - 1; i >= 0; --i) {
-#pragma unroll
-          for (int k = i + 1; k < NN; ++k) x[i] = fma(-w1[i][k], x[k], x[i]);
-          x[i] *= w1[i][i];
-        }
-#pragma unroll
-        for (int i = 0; i < NN; ++i) bp.put(RB::Z + j * NN + i, x[i]);
-      }
-      bp.close(RB::Z + NN * NN - 1);
-    }
-    HD_PHASE();
-    // ---- M1 = Ra W1^-1 (upper): row r solves x W1 = Ra[r,:] -> (x L) U = a ----
-    double m1[NN][NN];
-    {
-#pragma unroll
-      for (int r = 0; r < NN; ++r) {
-        double x[NN];
-#pragma unroll
-        for (int j = 0; j < NN; ++j) {  // z U = a (forward over columns)
-          double t = ra_at(sym_index<NN>(r, j));
-#pragma unroll
-          for (int k = 0; k < j; ++k) t = fma(-x[k], w1[k][j], t);
-          x[j] = t * w1[j][j];
-        }
-#pragma unroll
-        for (int j = NN - 1; j >= r; --j) {  // x L = z (backward, unit L): j >= r only
-          double t = x[j];
-#pragma unroll
-          for (int k = j + 1; k < NN; ++k) t = fma(-x[k], w1[k][j], t);
-          x[j] = t;
-        }
-#pragma unroll
-        for (int j = r; j < NN; ++j) m1[r][j] = x[j];
-      }
-    }
-    HD_PHASE();
-    // ---- Ra <- R~ + T~ P, P = M1 T~ (column by column) ; Sd <- T~ u + S- ----
-    {
-      double tl[NN][NN];
-      {
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < NN; ++i)
-#pragma unroll
-          for (int j = i; j < NN; ++j) tl[i][j] = rec(RL::T + (e++));
-      }
-      double rcn[NN];
-#pragma unroll
-      for (int i = 0; i < NN; ++i) rcn[i] = 0.0;
-      double* ldsd = reinterpret_cast<double*>(&stk[0][0]);
-#pragma unroll
-      for (int j = 0; j < NN; ++j) {
-        double pc[NN];
-#pragma unroll
-        for (int k = 0; k < NN; ++k) {
-          double t = 0.0;
-#pragma unroll
-          for (int m = 0; m < NN; ++m) t = fma(HD_SYM(m1, k, m), HD_SYM(tl, m, j), t);
-          pc[k] = t;
-        }
-#pragma unroll
-        for (int i = 0; i <= j; ++i) {
-          const int e = sym_index<NN>(i, j);
-          double t = rec(RL::R + e);
-#pragma unroll
-          for (int k = 0; k < NN; ++k) t = fma(HD_SYM(tl, i, k), pc[k], t);
-          ldsd[((e >> 1) * 64 + lt) * 2 + (e & 1)] = t;
-          rcn[i] = fma(t, Qc.g[j], rcn[i]);
-          if (i != j) rcn[j] = fma(t, Qc.g[i], rcn[j]);
-        }
-      }
-      double u[NN], sdn[NN];
-      sd_load(u);
-      double cs = 0.0;
-#pragma unroll
-      for (int i = 0; i < NN; ++i) {
-        double t = rec(RL::Sm + i) * sscale;
-#pragma unroll
-        for (int k = 0; k < NN; ++k) t = fma(HD_SYM(tl, i, k), u[k], t);
-        sdn[i] = t;
-        cs = fma(Qc.g[i], t, cs);
-      }
-      sd_store(sdn);
-      eb *= rec(RL::Tau + 1);
-      if (lc + 1 < L) {  // level lc+1 (top of layer lc+1): F_dn = rc . I+ + cs
-        PairOut bn{reinterpret_cast<double2*>(A.bsub) + (size_t)(lc + 1) * RB::pairs * nsc + sl,
-                   nsc, 0.0};
-#pragma unroll
-        for (int i = 0; i < NN; ++i) bn.put(RB::Rc + i, twopi * rcn[i]);
-        bn.close(RB::Rc + NN - 1);
-        bn.put(RB::Cs, fma(twopi, cs, f0mu0 * eb));
-        bn.close(RB::Cs);
-      }
-    }
-    HD_PHASE();
-  }
-
-  // ---- Lambertian surface: I+ = g x (hd_sweep_kernel's arithmetic) ----
-  double ra[NN][NN], sd[NN];
-  {
-    int e = 0;
-#pragma unroll
-    for (int i = 0; i < NN; ++i)
-#pragma unroll
-      for (int j = i; j < NN; ++j) ra[i][j] = ra_at(e++);
-    sd_load(sd);
-  }
-  // (surface inputs read here: nothing of them is live across the layer loop)
-  const double alb = A.albedo ? A.albedo[s] : 0.0;
-  if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
-  const double bsurf = A.planck ? A.planckv[(size_t)(L + 1) * nsc + sl] : 0.0;
-  const bool beam = f0mu0 > 0.0;
-  double gsd = 0.0, grg = 0.0;
-#pragma unroll
-  for (int i = 0; i < NN; ++i) {
-    gsd += Qc.g[i] * sd[i];
-#pragma unroll
-    for (int j = 0; j < NN; ++j) grg += Qc.g[i] * HD_SYM(ra, i, j) * Qc.g[j];
-  }
-  double esurf = (1.0 - alb) * bsurf;
-  const double dirsurf = f0mu0 * eb;
-  if (beam) esurf += alb * dirsurf / kPi;
-  const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
-  double chk = 0.0;
-  {
-    double up = 0.0, dn = 0.0;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) {
-      const double ipi = Qc.g[i] * x;
-      up += Qc.g[i] * ipi;
-      double t = sd[i];
-#pragma unroll
-      for (int j = 0; j < NN; ++j) t += HD_SYM(ra, i, j) * (Qc.g[j] * x);
-      dn += Qc.g[i] * t;
-    }
-    const double f0 = twopi * up, f1 = twopi * dn + dirsurf;
-    if (A.flux) {
-      double* fo = A.flux + (size_t)s * (L + 1) * 2;
-      fo[0] = f0;
-      fo[1] = f1;
-    }
-    if (A.fsurf) {
-      A.fsurf[sl] = f0;
-      A.fsurf[nsc + sl] = f1;
-    }
-    chk += f0 + f1;
-  }
-  A.xsurf[sl] = x;
-  if (!isfinite(chk)) st |= kStNonFinite;
-  if (st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
-}
-
-#endif  // HD_AB_VARIANTS
 
 // ============================================================================
 // K2 for nstr 4 and 8 (NN = 2, 4) in NN-lane teams: the adding sweep of
@@ -2190,19 +1763,6 @@ hipError_t launch_band_reduce(const BandArgs& ba, hipStream_t stream) {
 // ============================================================================
 // host side: constant tables + launchers
 // ============================================================================
-template <int NN>
-static void fill_quad(Quad<NN>& q, const QuadHost& h) {
-  for (int i = 0; i < NN; ++i) {
-    q.mu[i] = h.mu[i];
-    q.w[i] = h.w[i];
-    q.sd[i] = h.sd[i];
-    q.g[i] = h.g[i];
-    q.rmu[i] = 1.0 / h.mu[i];
-    q.rg[i] = 1.0 / h.g[i];
-    for (int l = 0; l < 2 * NN; ++l) q.pt[l][i] = h.pt[l][i];
-  }
-}
-
 // ---- warm-start eigenvectors of the team Jacobi (hd_kernels.hpp) ----
 namespace {
 typedef long double ld_t;
@@ -2339,15 +1899,6 @@ static void launch_sweep(const SweepArgs& sa, hipStream_t stream) {
       return;
     }
   }
-#if HD_AB_VARIANTS
-  if constexpr (NN == 8) {
-    if (sa.lean8) {
-      hipLaunchKernelGGL(hd_sweep_lean_kernel<NN>, dim3((unsigned)((sa.nsc + 63) / 64)), dim3(64),
-                         0, stream, sa);
-      return;
-    }
-  }
-#endif
   if (sa.nsc >= kNtMinSolves)
     hipLaunchKernelGGL((hd_sweep_kernel<NN, true>), dim3((unsigned)((sa.nsc + 63) / 64)), dim3(64),
                        0, stream, sa);
@@ -2474,19 +2025,6 @@ hipError_t launch_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
     launch_layer<NN>(la, stream);
     return hipGetLastError();
   });
-}
-hipError_t launch_column_nn(int nn, const LayerArgs& la, const SweepArgs& sa, hipStream_t stream) {
-#if HD_AB_VARIANTS
-  const dim3 grid((unsigned)((sa.nsc + 63) / 64)), block(64);
-  switch (nn) {
-    case 8: hipLaunchKernelGGL(hd_column_kernel<8>, grid, block, 0, stream, la, sa); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-#else
-  (void)nn, (void)la, (void)sa, (void)stream;
-  return hipErrorInvalidValue;  // A/B build only
-#endif
 }
 
 hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {

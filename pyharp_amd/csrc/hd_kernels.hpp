@@ -229,15 +229,9 @@ struct SweepArgs {
   // register path: the layer records' sources are for a unit beam at each layer
   // top (LayerArgs.tauc null); the sweep scales them by exp(-tau_c/mu0)
   int beam_scale;
-  // team path (nstr 18..32): the lean sweep (hd_team_mfma_sweep_lean_kernel, two waves
-  // per SIMD) instead of the one-wave-per-SIMD sweep
-  int lean;
   // register path, nstr 4 / 8: the sweep in NN-lane teams (hd_sweep_quad_kernel):
   // 1 on, 0 off, -1 for chunks of at most kQuadMaxSolves solves
   int quad;
-  // register path, nstr 16: the adding sweep with the stack state in LDS
-  // (hd_sweep_lean_kernel, two waves per SIMD) instead of hd_sweep_kernel
-  int lean8;
 };
 
 // hd_solve_flx (the full flux record per level, hdisort.h HD_FLX_*): what its sweep and
@@ -320,6 +314,20 @@ struct QuadHost {
   double pt[2 * kMaxNN][kMaxNN];
 };
 
+// host: the device quadrature table of one NN from the host quadrature
+template <int NN>
+inline void fill_quad(Quad<NN>& q, const QuadHost& h) {
+  for (int i = 0; i < NN; ++i) {
+    q.mu[i] = h.mu[i];
+    q.w[i] = h.w[i];
+    q.sd[i] = h.sd[i];
+    q.g[i] = h.g[i];
+    q.rmu[i] = 1.0 / h.mu[i];
+    q.rg[i] = 1.0 / h.g[i];
+    for (int l = 0; l < 2 * NN; ++l) q.pt[l][i] = h.pt[l][i];
+  }
+}
+
 // Warm start of the team layer kernel's Jacobi (hd_team_mfma.hip, nstr 18..32):
 // for every (ssa, chi_1) bin of a kWarmG x kWarmG grid on [0,1]^2, the
 // eigenvectors V0 of Sym = B0^T B0 of a Henyey-Greenstein layer at the bin
@@ -361,9 +369,6 @@ hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bo
 // register path, separately: the layer kernel and the adding sweep of one chunk
 hipError_t launch_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
 hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
-// register path, nstr 16: layer setup + adding sweep + back-substitution of one chunk in
-// one kernel (hd_column_kernel; la.scr unused -- no layer records)
-hipError_t launch_column_nn(int nn, const LayerArgs& la, const SweepArgs& sa, hipStream_t stream);
 // hd_solve_flx: the per-level prologue, the plain one-lane sweep and the back-substitution
 // with the second functional (register path), the one-wave team sweep with it (team path)
 hipError_t launch_flx_level(const FlxLevelArgs& fa, hipStream_t stream);
@@ -384,23 +389,15 @@ hipError_t launch_team_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs
                                       hipStream_t stream);
 hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp,
                                       const FlxArgs* fx, hipStream_t stream);
-// team path: the layer kernel and the sweep of one chunk
+// team path: the layer kernel and the sweep of one chunk (hd_team_mfma.hip)
 hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
 hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
 // the chunk epilogue of hd_solve_band (after the chunk's back-substitution)
 hipError_t launch_band_reduce(const BandArgs& ba, hipStream_t stream);
-// Kernel variants that were measured and not kept (the column
-// kernel, the LDS-state nstr-16 sweep, the one-wave team sweep, the VALU team layer
-// and sweep kernels, the per-angle radiance user kernel at nstr <= 16) are compiled
-// only into the A/B build (scripts/ab/build_variant.sh defines HD_AB_VARIANTS=1):
-// the product library carries only the kernels its dispatch can select.
-#ifndef HD_AB_VARIANTS
-#define HD_AB_VARIANTS 0
-#endif
-// A/B switches of the kernel variants (HD_JACOBI_WARM, HD_TEAM_SWEEP_LEAN, HD_SWEEP_QUAD,
-// HD_SWEEP_LEAN8, HD_RAD_USER, HD_TEAM_LAYER, HD_TEAM_SWEEP) are read only when the
-// single opt-in HD_AB=1 is set too: a stray variable in a user's environment never
-// changes which kernel runs (or the bits of the result).  Tests and the A/B scripts set it.
+// A/B switches between the kernels of the library (HD_JACOBI_WARM, HD_SWEEP_QUAD,
+// HD_BAND_CMAJ, HD_RAD_USER=rolled) are read only when the single opt-in HD_AB=1 is set
+// too: a stray variable in a user's environment never changes which kernel runs (or the
+// bits of the result).  Tests and the A/B scripts set it.
 inline const char* ab_env(const char* name) {
   const char* on = std::getenv("HD_AB");
   if (!on || on[0] != '1' || on[1] != '\0') return nullptr;

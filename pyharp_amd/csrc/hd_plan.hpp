@@ -11,7 +11,7 @@ namespace hd {
 
 constexpr int kMaxNN = 16;    // nstr <= 32
 constexpr int kMaxRegNN = 8;  // one-lane-per-problem kernels (hd_kernels.hip) up to nstr 16;
-                              // 16-lane team kernels (hd_team.hip) for nstr 18..32
+                              // 16-lane team kernels (hd_team_mfma.hip) for nstr 18..32
 
 // every group of record elements starts at an even element (RecL / RecB, hd_kernels.hpp)
 constexpr int even_up(int n) { return (n + 1) & ~1; }

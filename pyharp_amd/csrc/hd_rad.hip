@@ -1942,19 +1942,6 @@ static bool rad_user_rolled() {
   return v;
 }
 
-// HD_RAD_USER=direct: nstr <= 16 user angles by the per-angle hd_rad_user_kernel
-static bool rad_user_direct() {
-#if HD_AB_VARIANTS
-  static const bool v = [] {
-    const char* e = ab_env("HD_RAD_USER");
-    return e && std::strcmp(e, "direct") == 0;
-  }();
-  return v;
-#else
-  return false;  // the per-angle kernel at nstr <= 16: A/B build only
-#endif
-}
-
 template <int NN>
 static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
   const unsigned ns_b = (unsigned)((a.ns + 255) / 256);
@@ -1978,9 +1965,8 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
       a.umu_stride == 0;  // a team's four units share one user cosine: per-column rays
                           // take the one-lane user kernel
   // nstr <= 16 with radiances: the const kernel writes the angle-independent maps and
-  // the user angles run hd_rad_user_map_kernel (HD_AB=1 HD_RAD_USER=direct: the
-  // per-angle hd_rad_user_kernel)
-  const bool umap = NN <= kMaxRegNN && rad && !rad_user_direct();
+  // the user angles run hd_rad_user_map_kernel
+  const bool umap = NN <= kMaxRegNN && rad;
   RadArgs ac = a;
   ac.umap = umap ? 1 : 0;
   if (team_user) {
@@ -2002,7 +1988,7 @@ static void launch_rad(const RadArgs& a, bool radiances, hipStream_t st) {
                          dim3(64), 0, st, ac);
     else
 #endif
-    if constexpr (NN > kMaxRegNN || HD_AB_VARIANTS) {
+    if constexpr (NN > kMaxRegNN) {
       if (!team_user)
         hipLaunchKernelGGL(hd_rad_user_kernel<NN>, dim3((unsigned)((nr + 63) / 64), (unsigned)a.nm),
                            dim3(64), 0, st, a);

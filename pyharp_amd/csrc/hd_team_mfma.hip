@@ -1,18 +1,28 @@
-// hd_team_mfma.hip -- per-(solve, layer) setup for nstr 18..32 with the dense
-// 16 x 16 products on FP64 MFMA (v_mfma_f64_16x16x4_f64).
+// hd_team_mfma.hip -- the team path: the kernels of the discrete-ordinate solve for
+// nstr 18..32 (NN = nstr/2 in 9..16), where one problem's NN x NN matrices no longer fit
+// one lane's registers, with the dense 16 x 16 products on FP64 MFMA
+// (v_mfma_f64_16x16x4_f64), their table uploads and their launchers.
 //
 //   hd_team_mfma_layer_kernel<NN>  one wave = four (solve, layer) problems, the
-//                                  same per-layer setup as hd_team_layer_kernel
+//                                  same per-layer setup as hd_layer_kernel
 //                                  (delta-M, phase matrix, Cholesky + one-sided
 //                                  Jacobi eigenproblem, beam/thermal particular
 //                                  solutions, R~/T~/S~ in the flux-weighted
 //                                  basis)  [c_setdis,
 //                                  c_soleig, c_upbeam, c_upisot]
+//   hd_team_mfma_sweep_*_kernel    one wave = four solves: adding sweep top->bottom,
+//                                  Lambertian surface, back-substitution, level
+//                                  fluxes in harp layout  [c_setmtx, c_solve0,
+//                                  c_fluxes]
+//
+// Scratch records, solve-major inside a layer (a team's record is contiguous):
+//   layer ops [lc][s][2NN^2+2NN+2]  R~ rows | T~ rows | S~+ | S~- | tau' | pad
+//   back-sub  [lc][s][NN^2+2NN+1 -> even]  ZT rows | t | rc | cs | pad
 //
 // The work splits by shape:
 //   * sequential, one-problem-per-team algebra stays on the VALU in the team
-//     layout (T: team t = lanes 16t..16t+15, lane i holds row i): phase-matrix
-//     rows, the four Cholesky factorisations (S-, S+, I + Omega Omega^T,
+//     layout (T: team t = lanes 16t..16t+15, lane i holds row i; hd_team_prims.hpp):
+//     phase-matrix rows, the four Cholesky factorisations (S-, S+, I + Omega Omega^T,
 //     I + Psi^T Psi), their triangular inverses, the Jacobi sweeps and the
 //     vector recurrences of the particular solutions;
 //   * every dense 16 x 16 product runs on the matrix core in the MFMA layout
@@ -29,8 +39,8 @@
 //     the M layout, so chains of products need no data movement.  T <-> M goes
 //     through two LDS tile-sets per wave (row stride 17 doubles).
 //
-// Replaces the DPP-broadcast products of hd_team_layer_kernel, whose row
-// broadcasts, 64-bit selects and register spills were 39% of its VALU
+// The products were DPP row broadcasts on the VALU before: those,
+// their 64-bit selects and register spills were 39% of that kernel's VALU
 // instructions at one wave per SIMD (profiles/r02_c5_team_counters_v1.json).
 #include <cmath>
 #include <mutex>
@@ -654,12 +664,12 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_spher_kernel(LayerAr
 // dense 16 x 16 products (R A, A ZT, T (A ZT)) on the matrix core in the M
 // layout -- R~, T~ and A are symmetric, so each is its own transpose operand --
 // and the pivot-free LU of W1, the ZT solves and the vectors on the VALU in the
-// team layout (lane i = row i), as hd_team_sweep_kernel; W1 goes M -> T and ZT
-// T -> M through LDS, A is kept in both layouts.  Identical record formats, so
-// the back-substitution pass is hd_team_sweep_kernel's.  One wave per SIMD: at
+// team layout (lane i = row i); W1 goes M -> T and ZT
+// T -> M through LDS, A is kept in both layouts.  The back-substitution pass reads
+// its records in the team layout.  One wave per SIMD: at
 // two (256 registers) it spills 144 VGPRs and ran C5 at 0.81M solves/s against
-// 1.02M here and 0.97M for the VALU sweep (scripts/ab/sw_ab.sh).
-// As hd_solve's sweep it is in the A/B build only (the product runs the lean one).
+// 1.02M here and 0.97M for a VALU-product sweep.
+// hd_solve's sweep is the lean kernel below; this body runs as the flx and spher sweeps.
 // FLX (hd_solve_flx, always built): the back-substitution record is widened by the
 // mean-intensity row rh_i = sum_j A(i,j) h_j and the scalar ch = h . Sd, h = g / mu,
 // after cs (stride ne2tf), and the upward pass emits the eight components of every
@@ -974,13 +984,6 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
   }
 }
 
-#if HD_AB_VARIANTS  // hd_solve's one-wave team sweep: A/B build only
-template <int NN>
-__global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_kernel(SweepArgs A) {
-  __shared__ double lds[2 * kSet];
-  team_mfma_sweep_body<NN, false>(A, nullptr, lds);
-}
-#endif  // HD_AB_VARIANTS
 // hd_solve_flx's team sweep
 template <int NN>
 __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
@@ -998,7 +1001,7 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_spher_kernel(SweepAr
 
 // ============================================================================
 // K2 (team, MFMA), lean: the same sweep and back-substitution as
-// hd_team_mfma_sweep_kernel in at most 256 registers, so that two waves share a
+// team_mfma_sweep_body in at most 256 registers, so that two waves share a
 // SIMD (and one can run beside a 240-register layer-kernel wave) instead of one.
 // What changes is only where the operands live between their uses:
 //   * A's team rows (for the level's rc, and u = A t1 + Sd) stay in LDS tile set
@@ -1010,8 +1013,9 @@ __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_spher_kernel(SweepAr
 //     top of the layer (second reads of a record are L2 hits);
 //   * per-element record offsets are recomputed where they are used (laundered
 //     lane indices), not hoisted out of the layer loop.
-// The arithmetic and its order are hd_team_mfma_sweep_kernel's, so the records
-// and fluxes are bitwise the same (tests/test_gpu_parity.py: lean vs default).
+// The arithmetic and its order are team_mfma_sweep_body's, so the records and fluxes
+// are bitwise the same (profiles/r06/parity/pytest_ab.log: the last run against
+// hd_solve's one-wave sweep, at 31f114a).
 // ============================================================================
 template <int NN, bool NT>
 __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArgs A) {
@@ -1169,7 +1173,7 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArg
       sfor<0, NN>([&](auto K) { u = fma(ar[HD_K(K)] * msk, bc<HD_K(K)>(t1), u); });
     }
     bw[NN * NN + ii] = t1;
-    // columns of L^-1 and U^-1 from the LU rows (hd_team_mfma_sweep_kernel)
+    // columns of L^-1 and U^-1 from the LU rows (team_mfma_sweep_body)
     {
       double zl[NN], zu[NN];
       sfor<0, NN>([&](auto R) {
@@ -1690,7 +1694,7 @@ __global__ __launch_bounds__(64, 2) void hd_rad_team_layer_kernel(RadArgs A) {
 // back-substitution (hd_rad_sweep_kernel: the stack state R_above/S_down and
 // I+/I- kept at every level) on the team layout with the dense products on the
 // matrix core -- four units (solve, azimuthal mode) per wave, the arithmetic of
-// hd_team_mfma_sweep_kernel above.  The layer-operator and back-substitution
+// team_mfma_sweep_body above.  The layer-operator and back-substitution
 // records (rsw, bsub) are unit-contiguous at these sizes ([layer][unit][element]:
 // a team's loads and stores of one unit's record hit neighbouring lines, where the
 // unit-fastest layout the one-lane kernels use put every lane on its own line);
@@ -1978,12 +1982,24 @@ hipError_t upload_warm_tables_team(const QuadHost* per_nn) {
                            hipMemcpyHostToDevice);
 }
 
-hipError_t upload_quad_tables_team_mfma(const QuadTablesTeam& t) {
+hipError_t upload_quad_tables_team(const QuadHost* per_nn /* [kMaxNN], index nn-1 */) {
+  QuadTablesTeam t;
+  fill_quad<9>(t.q9, per_nn[8]);
+  fill_quad<10>(t.q10, per_nn[9]);
+  fill_quad<11>(t.q11, per_nn[10]);
+  fill_quad<12>(t.q12, per_nn[11]);
+  fill_quad<13>(t.q13, per_nn[12]);
+  fill_quad<14>(t.q14, per_nn[13]);
+  fill_quad<15>(t.q15, per_nn[14]);
+  fill_quad<16>(t.q16, per_nn[15]);
   return hipMemcpyToSymbol(HIP_SYMBOL(c_qt), &t, sizeof(t), 0, hipMemcpyHostToDevice);
 }
 
+// the layer kernel and the sweep of one chunk (hd_solve launches them on one stream, or
+// chunk k+1's layer kernel on one stream beside chunk k's sweep on another)
 template <int NN>
 static hipError_t launch_layer(const LayerArgs& la, hipStream_t stream) {
+  static_assert(ne1t<NN>() % 2 == 0 && ne2t<NN>() % 2 == 0, "16-byte aligned records");
   const unsigned nb1 = (unsigned)(((la.nsc + 3) / 4) * (long)la.nlyr);
   if (la.nsc >= kNtMinSolves)
     hipLaunchKernelGGL((hd_team_mfma_layer_kernel<NN, true>), dim3(nb1), dim3(64), 0, stream, la);
@@ -1995,19 +2011,14 @@ static hipError_t launch_layer(const LayerArgs& la, hipStream_t stream) {
 template <int NN>
 static hipError_t launch_sweep(const SweepArgs& sa, hipStream_t stream) {
   const dim3 gl((unsigned)((sa.nsc + 3) / 4));
-  if (sa.lean && sa.nsc >= kNtMinSolves)
+  if (sa.nsc >= kNtMinSolves)
     hipLaunchKernelGGL((hd_team_mfma_sweep_lean_kernel<NN, true>), gl, dim3(64), 0, stream, sa);
-  else if (sa.lean)
-    hipLaunchKernelGGL((hd_team_mfma_sweep_lean_kernel<NN, false>), gl, dim3(64), 0, stream, sa);
-#if HD_AB_VARIANTS
   else
-    hipLaunchKernelGGL(hd_team_mfma_sweep_kernel<NN>, dim3((unsigned)((sa.nsc + 3) / 4)), dim3(64),
-                       0, stream, sa);
-#endif
+    hipLaunchKernelGGL((hd_team_mfma_sweep_lean_kernel<NN, false>), gl, dim3(64), 0, stream, sa);
   return hipGetLastError();
 }
 
-hipError_t launch_team_sweep_mfma(int nn, const SweepArgs& sa, hipStream_t stream) {
+hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {
   return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
       nn, [&](auto NN) { return launch_sweep<NN>(sa, stream); });
 }
@@ -2054,7 +2065,7 @@ hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs
   });
 }
 
-hipError_t launch_team_layer_mfma(int nn, const LayerArgs& la, hipStream_t stream) {
+hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
   return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
       nn, [&](auto NN) { return launch_layer<NN>(la, stream); });
 }

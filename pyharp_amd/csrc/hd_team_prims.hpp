@@ -1,5 +1,5 @@
-// hd_team_prims.hpp -- the 16-lane team primitives shared by the team kernels
-// (hd_team.hip: VALU products; hd_team_mfma.hip: FP64 MFMA products).
+// hd_team_prims.hpp -- the 16-lane team primitives of the team kernels
+// (hd_team_mfma.hip).
 //
 // Team layout: a team is one DPP row (16 lanes of a wave64); lane i owns row i
 // of every NN x NN matrix and element i of every vector (lanes i >= NN carry
@@ -25,8 +25,7 @@ struct QuadTablesTeam {
   Quad<15> q15;
   Quad<16> q16;
 };
-// each translation unit keeps its own __constant__ copy (no relocatable device
-// code) and passes it here
+// the translation unit's __constant__ copy goes in here
 template <int NN>
 __device__ __forceinline__ const Quad<NN>& tquad(const QuadTablesTeam& t) {
   if constexpr (NN == 9) return t.q9;
@@ -39,20 +38,11 @@ __device__ __forceinline__ const Quad<NN>& tquad(const QuadTablesTeam& t) {
   else return t.q16;
 }
 
-// host: the team tables from the per-nn host quadrature (hd_team.hip)
-void fill_quad_tables_team(const QuadHost* per_nn /* [kMaxNN], index nn-1 */, QuadTablesTeam& t);
-
-// hd_team_mfma.hip: its copy of the team tables, and the MFMA layer kernel
-hipError_t upload_quad_tables_team_mfma(const QuadTablesTeam& t);
 hipError_t upload_warm_tables_team(const QuadHost* per_nn);  // team Jacobi warm start
-hipError_t launch_team_layer_mfma(int nn, const LayerArgs& la, hipStream_t stream);
-hipError_t launch_team_sweep_mfma(int nn, const SweepArgs& sa, hipStream_t stream);
 
 namespace team {
 
 constexpr int kTeam = 16;
-constexpr int kTeamBlock = 256;
-constexpr int kTeamsPerBlock = kTeamBlock / kTeam;
 
 // ---- compile-time loops (DPP controls must be immediates) -------------------
 template <int B, class F, int... Is>
@@ -185,22 +175,6 @@ __device__ __forceinline__ void team_usolve(const double (&lt)[NN], double rd, d
     if (i == k) x *= rd;
     const double xk = bc<k>(x);
     if (i < k) x = fma(-lt[k], xk, x);
-  });
-}
-
-// X <- L^-T X  (X rows distributed)
-template <int NN>
-__device__ __forceinline__ void team_umsolve(const double (&lt)[NN], double rd, double (&x)[NN]) {
-  const int i = tlane();
-  sfor_rev<0, NN>([&](auto K) {
-    constexpr int k = HD_K(K);
-    const double sc = i == k ? rd : 1.0;
-    sfor<0, NN>([&](auto J) { x[HD_K(J)] *= sc; });
-    const double m = i < k ? lt[k] : 0.0;
-    sfor<0, NN>([&](auto J) {
-      constexpr int j = HD_K(J);
-      x[j] = fma(-m, bc<k>(x[j]), x[j]);
-    });
   });
 }
 

@@ -6,7 +6,7 @@
 set -e
 C=pyharp_amd/csrc
 CACHE=${OBJCACHE:-/tmp/objcache}
-ALL="hd_kernels.hip hd_team.hip hd_team_mfma.hip hd_rad.hip hd_harp.hip hd_api.cpp hd_ncread.cpp hd_rad_wide.hip"
+ALL="hd_kernels.hip hd_team_mfma.hip hd_rad.hip hd_harp.hip hd_api.cpp hd_ncread.cpp hd_rad_wide.hip"
 flags_of() { [ $1 = hd_team_mfma.hip ] && echo "-mllvm -disable-machine-licm"; }
 if [ "$1" = --cache ]; then
   mkdir -p $CACHE

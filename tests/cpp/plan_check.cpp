@@ -23,7 +23,7 @@ static int g_fail = 0;
 static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
 
 // The record sizes, written out from the kernels' record layouts (hd_kernels.hpp RecL /
-// RecB / RecBF; hd_team.hip's rows): not through the header under test.
+// RecB / RecBF; the team path's rows): not through the header under test.
 static size_t ne1_ref(int nn) {
   if (nn <= 8) return 2 * even((size_t)nn * (nn + 1) / 2) + 2 * even(nn) + 2;
   return 2 * (size_t)nn * nn + 2 * nn + 2;

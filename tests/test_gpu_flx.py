@@ -149,6 +149,33 @@ def test_consistent_with_hd_solve(golden, nstr, source):
                                flx[..., IUAVGSO], rtol=1e-15, atol=0.0)
 
 
+@pytest.mark.parametrize("chunk", [0, 23])
+@pytest.mark.parametrize("nstr", [18, 32])
+def test_team_flup_bitwise_with_hd_solve(nstr, chunk):
+    """Team path: hd_solve's sweep (two waves per SIMD, its operands parked in LDS and
+    re-read from the records) and the one-wave sweep body of hd_solve_flx do the same
+    arithmetic in the same order, so the upward fluxes agree to the bit -- with a beam and
+    Planck emission, in one chunk and in chunks of 23 of the 93 solves."""
+    from pyharp_amd.disort import _context
+    nwave, ncol, nlyr = 3, 31, 14
+    rng = np.random.default_rng(1800 + nstr)
+    prop, bc = _hg_batch(rng, nwave, ncol, nlyr, nstr)
+    bc.update(btemp=np.full((nwave, ncol), 290.0), ttemp=np.full((nwave, ncol), 160.0),
+              temis=rng.uniform(0.1, 0.9, (nwave, ncol)))
+    temf = np.linspace(285.0, 190.0, nlyr + 1)[None, :] + rng.uniform(-5, 5, (ncol, nlyr + 1))
+    wl, wu = [200.0, 600.0, 1000.0], [400.0, 900.0, 1100.0]
+    d = _disort(nstr, nlyr, nwave, ncol, planck=True, wl=wl, wu=wu)
+    ctx = _context(0)
+    ctx.set_chunk(chunk)
+    try:
+        flx = _flx(d, prop, bc, temf)
+        f = _flux(d, prop, bc, temf)
+    finally:
+        ctx.set_chunk(0)
+    assert np.all(np.isfinite(f)) and np.all(f[..., 0] > 0.0)
+    assert np.array_equal(flx[..., IFLUP], f[..., 0])
+
+
 # --------------------------------------------------------------------------- #
 # lane / wave / chunk edges: a solve's record does not depend on where it ran
 # --------------------------------------------------------------------------- #
