@@ -3,13 +3,18 @@
 // one lane's registers, with the dense 16 x 16 products on FP64 MFMA
 // (v_mfma_f64_16x16x4_f64), their table uploads and their launchers.
 //
-//   hd_team_mfma_layer_kernel<NN>  one wave = four (solve, layer) problems, the
+//   team_layer_body<NN, Path>      one wave = four (problem, layer) setups, the
 //                                  same per-layer setup as hd_layer_kernel
 //                                  (delta-M, phase matrix, Cholesky + one-sided
 //                                  Jacobi eigenproblem, beam/thermal particular
 //                                  solutions, R~/T~/S~ in the flux-weighted
 //                                  basis)  [c_setdis,
-//                                  c_soleig, c_upbeam, c_upisot]
+//                                  c_soleig, c_upbeam, c_upisot].  Stated once;
+//                                  its three kernels declare the LDS and name a path:
+//     hd_team_mfma_layer_kernel<NN, NT>        FluxLayerPath<NT, false>: problem = solve
+//     hd_team_mfma_layer_spher_kernel<NN, NT>  FluxLayerPath<NT, true>: pseudo-spherical beam
+//     hd_rad_team_layer_kernel<NN>             RadLayerPath: problem = (solve, azimuthal
+//                                              mode), the radiance records kept
 //   hd_team_mfma_sweep_*_kernel    one wave = four solves: adding sweep top->bottom,
 //                                  Lambertian surface, back-substitution, level
 //                                  fluxes in harp layout  [c_setmtx, c_solve0,
@@ -218,21 +223,145 @@ __device__ __forceinline__ double team_matvec(const double (&xr)[NN], double x) 
   return y;
 }
 
+// ---- the paths of team_layer_body ------------------------------------------------
+// A path names its kernel's argument struct, how many problems a chunk holds and the
+// stride of its per-solve arrays, and switches the parts of the body that are not
+// common.  kModes: the problem is a unit u = m * ns + sl of azimuthal mode m (else a
+// solve, m = 0) -- Y_l^m phase rows from c_rtt in place of the Legendre recurrence,
+// beam source x (2 - delta_m0), thermal source at m = 0 only, V = L^-1 U formed
+// before W (below), the radiance record rrd kept, R~/T~ stored packed upper to rsw.
+// kSpher: the pseudo-spherical beam, as hd_kernels.hip's
+// layer_body -- hd_spher_kernel's secant lambda in place of 1/mu0, exp(-ch'_top) at
+// the layer top.  kNT: nontemporal R~/T~ stores.  kWarm, kThin and kSecant switch
+// the Jacobi warm start, the thin-thermal-layer form and the resonance secant move
+// (else the kResClamp clamp) -- DESIGN.md sections 3f and 10 item 6.
+template <bool NT, bool SPHER>
+struct FluxLayerPath {
+  using Args = LayerArgs;
+  static constexpr bool kModes = false, kSpher = SPHER, kNT = NT;
+  static constexpr bool kWarm = true, kThin = true, kSecant = !SPHER;
+  static __device__ __forceinline__ int problems(const Args& A) { return A.nsc; }
+  static __device__ __forceinline__ int solves(const Args& A) { return A.nsc; }
+};
+struct RadLayerPath {
+  using Args = RadArgs;
+  static constexpr bool kModes = true, kSpher = false, kNT = false;
+  static constexpr bool kWarm = false, kThin = false, kSecant = false;
+  static __device__ __forceinline__ int problems(const Args& A) { return A.nu; }
+  static __device__ __forceinline__ int solves(const Args& A) { return A.ns; }
+};
+
+// Phase-matrix rows of a flux path (m = 0): S+ = -A+ (ap), S- = -A- (lch) before the
+// quadrature scaling, and the beam source sums xs, xd; Legendre P_l(mu0) by recurrence
+template <int NN>
+__device__ __forceinline__ void phase_rows_legendre(const double* q, int nm, double f, double rf,
+                                                    double mub, int ii, double msk, int t, int i,
+                                                    double* G, double (&ap)[NN], double (&lch)[NN],
+                                                    double& xs, double& xd) {
+  constexpr int N = 2 * NN;
+  const Quad<NN>& Qc = tquad<NN>(c_qt);
+  // chi_1 .. chi_{N-1} of the team's record staged in LDS (the G area, free until the
+  // eigenvalues): lane i of team t loads chi_{i+1} and chi_{i+17}, one round trip for the
+  // whole record instead of one per iteration of the loop below
+  {
+    double* gm = G + t * 32;
+    const int l1 = i + 1, l2 = i + 1 + 16;
+    gm[i] = (l1 < N && l1 <= nm) ? q[1 + l1] : 0.0;
+    gm[16 + i] = (l2 < N && l2 <= nm) ? q[1 + l2] : 0.0;
+    lds_fence();
+  }
+  double pprev = 0.0, pcur = 1.0;
+  const double* gm = G + t * 32 - 1;  // gm[l] = chi_l
+#pragma nounroll
+  for (int l2 = 0; l2 < NN; ++l2) {
+    const int le = 2 * l2, lo = le + 1;
+    const double che = le == 0 ? 1.0 : gm[le];
+    const double cho = gm[lo];
+    const double ge = (2 * le + 1) * (che - f) * rf;
+    const double go = (2 * lo + 1) * (cho - f) * rf;
+    const double pe0 = pcur;
+    const double po0 = ((2 * lo - 1) * mub * pcur - (lo - 1) * pprev) / lo;
+    pprev = po0;
+    pcur = ((2 * lo + 1) * mub * po0 - lo * pe0) / (lo + 1);
+    const double ue = ge * Qc.pt[le][ii] * msk;
+    const double uo = go * Qc.pt[lo][ii] * msk;
+    xs = fma(ue, pe0, xs);
+    xd = fma(uo, po0, xd);
+    sfor<0, NN>([&](auto J) {
+      constexpr int j = HD_K(J);
+      ap[j] = fma(ue, Qc.pt[le][j], ap[j]);
+      lch[j] = fma(uo, Qc.pt[lo][j], lch[j]);
+    });
+  }
+}
+// The same for azimuthal mode m (the parity of l+m takes the place of that of l):
+// Y_l^m(mu0) by recurrence, Y_l^m(mu_i) from the tables, the row's other nodes by
+// broadcast
+template <int NN>
+__device__ __forceinline__ void phase_rows_mode(const double* q, int nm, double f, double rf,
+                                                double mub, int m, int ii, double msk,
+                                                double (&ap)[NN], double (&lch)[NN], double& xs,
+                                                double& xd) {
+  const int mp = m & 1;
+  const double* lam = rad_lam<NN>(m);
+  const double sx = sqrt(fmax(0.0, 1.0 - mub * mub));
+  double seed = c_rtt.seed[m];
+  for (int a = 0; a < m; ++a) seed *= sx;  // Y_m^m(mu0)
+  double y1 = 0.0, y2 = 0.0;                // Y_{l-1}^m(mu0), Y_{l-2}^m(mu0)
+#pragma nounroll
+  for (int l2 = 0; l2 < NN; ++l2) {
+    const int la = 2 * l2, lb = la + 1;
+    const double ya =
+        la < m ? 0.0 : (la == m ? seed : fma(c_rtt.ra[m][la] * mub, y1, -c_rtt.rb[m][la] * y2));
+    y2 = y1;
+    y1 = ya;
+    const double yb =
+        lb < m ? 0.0 : (lb == m ? seed : fma(c_rtt.ra[m][lb] * mub, y1, -c_rtt.rb[m][lb] * y2));
+    y2 = y1;
+    y1 = yb;
+    const int le = mp ? lb : la, lo = mp ? la : lb;
+    const double pe0 = mp ? yb : ya, po0 = mp ? ya : yb;
+    const double che = le == 0 ? 1.0 : (le <= nm ? q[1 + le] : 0.0);
+    const double cho = lo == 0 ? 1.0 : (lo <= nm ? q[1 + lo] : 0.0);
+    const double ge = (2 * le + 1) * (che - f) * rf;
+    const double go = (2 * lo + 1) * (cho - f) * rf;
+    const double te = lam[le * NN + ii] * msk;  // Y_le^m(mu_i), this lane's node
+    const double to = lam[lo * NN + ii] * msk;
+    const double ue = ge * te;
+    const double uo = go * to;
+    xs = fma(ue, pe0, xs);
+    xd = fma(uo, po0, xd);
+    sfor<0, NN>([&](auto J) {
+      constexpr int j = HD_K(J);
+      ap[j] = fma(ue, bc<j>(te), ap[j]);
+      lch[j] = fma(uo, bc<j>(to), lch[j]);
+    });
+  }
+}
+
 }  // namespace
 
 // ============================================================================
-// K1 (team, MFMA): per-(solve, layer) setup, four problems per wave
+// K1 (team, MFMA): per-(problem, layer) setup, four problems per wave -- the one
+// body behind hd_team_mfma_layer_kernel, hd_team_mfma_layer_spher_kernel
+// (FluxLayerPath) and hd_rad_team_layer_kernel (RadLayerPath)
 // ============================================================================
-// SPHER (pseudo-spherical beam): as hd_kernels.hip's layer_body --
-// hd_spher_kernel's secant lambda in place of 1/mu0, exp(-ch'_top) at the layer top.
 // (The arguments by value and the LDS from the kernel: with LayerArgs by reference
 // hd_team_mfma_layer_kernel compiled to one or two more VGPRs at every NN.)
-template <int NN, bool NT, bool SPHER>
-__device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs* P, double* lds) {
+template <int NN, class Path>
+__device__ __forceinline__ void team_layer_body(typename Path::Args A, const SphArgs* P,
+                                                double* lds) {
   double* S0 = lds;
   double* S1 = lds + kSet;
   double* G = lds + 2 * kSet;  // [t][dsq | gsq][16]
   constexpr int N = 2 * NN;
+  // the records of a kModes path: rsw (NE1 doubles a unit) and rrd (NR, offsets o*)
+  constexpr int nsym = NN * (NN + 1) / 2;
+  constexpr int NE1 = rad_layer_record_doubles(NN);
+  constexpr int NR = rad_rec_doubles(NN);
+  constexpr int oV = nsym, oK = nsym + NN * NN, oZp = oK + NN, oZm = oZp + NN, oH = oZm + NN;
+  constexpr int oBt = oH + NN, oSl = oBt + 1, oTp = oSl + 1, oOm = oTp + 1, oEk = oOm + 1;
+  constexpr int oE0 = oEk + NN;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
   const int lane = (int)threadIdx.x;
   const int h = lane >> 4, c = lane & 15;  // M layout
@@ -240,20 +369,34 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
   const bool act = i < NN;
   const int ii = act ? i : 0;
   const int L = A.nlyr;
-  // block = 4 consecutive solves (one per team) of one layer: their records are
-  // contiguous.  Blocks are numbered layer-fastest within a group of solves and
+  const int npb = Path::problems(A);  // problems in this chunk (= record stride)
+  const int ns = Path::solves(A);     // solves in this chunk (= stride of planckv, tauc, chp)
+  // block = 4 consecutive problems (one per team) of one layer: their records are
+  // contiguous.  Blocks are numbered layer-fastest within a group of problems and
   // dealt to one XCD (blocks b and b + 8 share an L2), so the neighbouring
   // layers of a solve -- which share prop's cache lines -- are read close together
-  const int grp = block_group(L);  // first solve of this block / 4
+  const int grp = block_group(L);  // first problem of this block / 4
   const int lc = block_layer(L);
   // every lane takes part in the MFMA and LDS exchanges: a team past the end
-  // recomputes the block's first solve and stores nothing
-  const bool valid = grp * 4 + t < A.nsc;
-  const int sl = valid ? grp * 4 + t : grp * 4;
+  // recomputes the block's first problem and stores nothing
+  const bool valid = grp * 4 + t < npb;
+  const int u = valid ? grp * 4 + t : grp * 4;
+  const int m = Path::kModes ? u / ns : 0;
+  const int sl = u - m * ns;
   const long s = A.s0 + sl;
   const int nm = A.nmom;
   const int np = A.nprop;
+  const bool wr = valid && act;
   int st = 0;
+  int um[4];  // team tt's problem, for the stores of the M layout
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) um[tt] = grp * 4 + tt < npb ? grp * 4 + tt : grp * 4;
+  double* rr = nullptr;   // kModes: element e of this team's rrd record is rr[e]
+  double* out = nullptr;  // kModes: element e of unit v's rsw record is out[v * NE1 + e]
+  if constexpr (Path::kModes) {
+    rr = A.rrd + ((size_t)lc * npb + u) * NR;
+    out = A.rsw + (size_t)lc * NE1 * npb;
+  }
 
   // padding columns (>= NN) of both tile-sets are zero for the whole kernel
   // except where a product's identity padding lands (block diagonal: harmless)
@@ -284,51 +427,21 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
   bool beam = fb > 0.0 && mu0 > 0.0;
   if (fb > 0.0 && !(mu0 > 0.0 && mu0 <= 1.0)) st |= kStBadInput;  // cdisort c_chekin
   double rmu0 = beam ? 1.0 / mu0 : 0.0;
-  if constexpr (SPHER) {
-    beam = beam && P->chp[(size_t)(L + 1) * A.nsc + sl] != 0.0;
-    rmu0 = beam ? P->lam[(size_t)lc * A.nsc + sl] : 0.0;
+  if constexpr (Path::kSpher) {
+    beam = beam && P->chp[(size_t)(L + 1) * ns + sl] != 0.0;
+    rmu0 = beam ? P->lam[(size_t)lc * ns + sl] : 0.0;
   }
   const double mub = beam ? mu0 : 0.0;
+  const bool therm = A.planck && m == 0;
 
   // ---- phase-matrix rows: S+ = -A+ (ap), S- = -A- (lch); beam source sums ----
-  // chi_1 .. chi_{N-1} of the team's record staged in LDS (the G area, free until the
-  // eigenvalues): lane i of team t loads chi_{i+1} and chi_{i+17}, one round trip for the
-  // whole record instead of one per iteration of the loop below
-  {
-    double* gm = G + t * 32;
-    const int l1 = i + 1, l2 = i + 1 + 16;
-    gm[i] = (l1 < N && l1 <= nm) ? q[1 + l1] : 0.0;
-    gm[16 + i] = (l2 < N && l2 <= nm) ? q[1 + l2] : 0.0;
-    lds_fence();
-  }
   double ap[NN], lch[NN];
   double xs = 0.0, xd = 0.0;
   sfor<0, NN>([&](auto J) { ap[HD_K(J)] = lch[HD_K(J)] = 0.0; });
-  {
-    double pprev = 0.0, pcur = 1.0;
-    const double* gm = G + t * 32 - 1;  // gm[l] = chi_l
-#pragma nounroll
-    for (int l2 = 0; l2 < NN; ++l2) {
-      const int le = 2 * l2, lo = le + 1;
-      const double che = le == 0 ? 1.0 : gm[le];
-      const double cho = gm[lo];
-      const double ge = (2 * le + 1) * (che - f) * rf;
-      const double go = (2 * lo + 1) * (cho - f) * rf;
-      const double pe0 = pcur;
-      const double po0 = ((2 * lo - 1) * mub * pcur - (lo - 1) * pprev) / lo;
-      pprev = po0;
-      pcur = ((2 * lo + 1) * mub * po0 - lo * pe0) / (lo + 1);
-      const double ue = ge * Qc.pt[le][ii] * msk;
-      const double uo = go * Qc.pt[lo][ii] * msk;
-      xs = fma(ue, pe0, xs);
-      xd = fma(uo, po0, xd);
-      sfor<0, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        ap[j] = fma(ue, Qc.pt[le][j], ap[j]);
-        lch[j] = fma(uo, Qc.pt[lo][j], lch[j]);
-      });
-    }
-  }
+  if constexpr (Path::kModes)
+    phase_rows_mode<NN>(q, nm, f, rf, mub, m, ii, msk, ap, lch, xs, xd);
+  else
+    phase_rows_legendre<NN>(q, nm, f, rf, mub, ii, msk, t, i, G, ap, lch, xs, xd);
   sfor<0, NN>([&](auto J) {
     constexpr int j = HD_K(J);
     const double diag = i == j ? rmu_i : 0.0;
@@ -339,10 +452,21 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
   // L L^T = S-
   double lt[NN], rdl;
   if (!team_chol<NN, true>(lch, lt, rdl)) st |= kStEigen;
+  if constexpr (Path::kModes) {
+    // L, packed lower row-major: row i holds lch[k], k <= i.  Branch-free: the
+    // elements a lane does not own go to the sink.  Stores under a lane-dependent
+    // condition inside the unrolled loop cost 1 KB of spill at two waves per SIMD
+    double* lrow = rr + i * (i + 1) / 2;
+    sfor<0, NN>([&](auto K) {
+      constexpr int k = HD_K(K);
+      double* dst = (wr && k <= i) ? &lrow[k] : A.sink + lane;
+      *dst = lch[k];
+    });
+  }
 
   // ---- pre-Jacobi vectors (depend on L only) ----
   double w2 = 0.0, lxd = 0.0;  // w2 = L^-T L^-1 g rv: V^T (L^-1 g rv) = U^T w2 later
-  const double fb2 = fb * (0.5 / kPi);
+  const double fb2 = fb * ((m == 0 ? 0.5 : 1.0) / kPi);
   if (beam) {
     const double y = sd_i * (fb2 * xs);
     double z = 0.0;  // z = L^T y
@@ -357,22 +481,44 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     team_lsolve<NN>(lch, rdl, lxd);
     team_usolve<NN>(lt, rdl, lxd);
   }
+  // ---- thermal source (c_upisot): cvec, and h = L^-T L^-1 (sd mu) / g ----
   double cvec = 0.0, db = 0.0, bsum = 0.0;
   bool thin = false;  // 0 < tau' < kThinTau under a Planck source (hd_device.hpp)
-  if (A.planck) {
-    const double bt = A.planckv[(size_t)(L - lc) * A.nsc + sl];
+  if (therm) {
+    const double bt = A.planckv[(size_t)(L - lc) * ns + sl];
     // a transparent layer carries its top level's Planck value through
     // (c_disort's xr1 = 0 when dtaucpr = 0: B(tau) = xr0 = B_top)
-    const double bb = taup > 0.0 ? A.planckv[(size_t)(L - lc - 1) * A.nsc + sl] : bt;
+    const double bb = taup > 0.0 ? A.planckv[(size_t)(L - lc - 1) * ns + sl] : bt;
     db = bb - bt;
     bsum = bt + bb;
     const double b1 = taup > 0.0 ? 2.0 * db / taup : 0.0;
-    thin = taup > 0.0 && taup < kThinTau;
+    thin = Path::kThin && taup > 0.0 && taup < kThinTau;
     cvec = sd_i * mu_i;
     team_lsolve<NN>(lch, rdl, cvec);
     team_usolve<NN>(lt, rdl, cvec);
+    if constexpr (Path::kModes) {
+      if (wr) rr[oH + i] = rg_i * cvec;  // h
+    }
     // a thin layer keeps the slope part 2 (dB/tau') h alone here: Q~- takes it below
     cvec = fma(b1 * rg_i, cvec, thin ? 0.0 : db) * msk;
+    if constexpr (Path::kModes) {
+      if (valid && i == 0) {
+        rr[oBt] = bt;
+        rr[oSl] = 0.5 * b1;
+      }
+    }
+  } else if constexpr (Path::kModes) {
+    if (wr) rr[oH + i] = 0.0;
+    if (valid && i == 0) {
+      rr[oBt] = 0.0;
+      rr[oSl] = 0.0;
+    }
+  }
+  if constexpr (Path::kModes) {
+    if (valid && i == 0) {
+      rr[oTp] = taup;
+      rr[oOm] = om;
+    }
   }
   {
     double z[NN];
@@ -387,16 +533,18 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     if (!team_chol<NN, false>(ap, unused, rdc)) st |= kStEigen;  // ap <- rows of C
     sfor<0, NN>([&](auto I) {
       constexpr int r = HD_K(I);
-      double u = 0.0;
-      sfor<r, NN>([&](auto K) { u = fma(bc<HD_K(K)>(ap[r]), lt[HD_K(K)], u); });
-      bcol[r] = u;
+      double uu = 0.0;
+      sfor<r, NN>([&](auto K) { uu = fma(bc<HD_K(K)>(ap[r]), lt[HD_K(K)], uu); });
+      bcol[r] = uu;
       pin<NN>(ap);
     });
     // Warm start (hd_kernels.hpp): B0 <- B0 V0 on the matrix core, V0 the
     // tabulated eigenvectors of each team's (ssa, chi_1) bin (identity for a
     // non-scattering layer), read straight into the M layout; S1 is free until
     // C^-T is written to it below
-    if (A.warm) {
+    bool warm = false;
+    if constexpr (Path::kWarm) warm = A.warm;
+    if (warm) {
       const double g1 = nm >= 1 ? q[2] : 0.0;
       const int e = ssa > 0.0 ? warm_bin(ssa) * kWarmG + warm_bin(g1) : kWarmG * kWarmG;
       int es[4];
@@ -445,30 +593,60 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     kk = sqrt(k2 > 0.0 ? k2 : 0.0) * msk;
     // Delta = tanh(k tau'/2)/k, Gamma = k tanh(k tau'/2) (lane j)
     const double x = kk * taup;
-    const double m = -expm1(-x);
-    const double th = m * rcp_nr(2.0 - m);
+    const double mm = -expm1(-x);
+    const double th = mm * rcp_nr(2.0 - mm);
     const double delta = x > 1.0e-8 ? th * rcp_nr(kk > 0.0 ? kk : 1.0) : 0.5 * taup;
     G[t * 32 + i] = sqrt(delta) * msk;
     G[t * 32 + 16 + i] = sqrt(kk * th) * msk;
+    if constexpr (Path::kModes) {
+      if (wr) {
+        rr[oK + i] = kk;
+        rr[oEk + i] = 1.0 - mm;  // exp(-k tau')
+      }
+    }
   }
 
   // ---- the dense products on the matrix core; vectors of the beam solution ----
   // LDS holds what the next phase reads: S0 = L^-T rows, then W; S1 = C^-T rows,
-  // then B^T rows, then U^T (whose rows and columns feed the two beam matvecs)
+  // then B^T rows, then U^T (whose rows and columns feed the two beam matvecs).
+  // The order is the path's: a flux path forms W = L^-T L^-1 first.  kModes keeps
+  // L^-T in S0 until V = L^-1 U is formed and stored, and forms W after it from the
+  // same rows (no M-layout copy of L^-T or W held across the products: the kernel
+  // sits at the register cap of two waves per SIMD)
   double zp = 0.0, zm = 0.0, e0 = 0.0;
   double wth = 0.0;  // thin thermal layer: Omega Omega^T (g x slope part), see ga below
   {
     double X[4][4], Y[4][4], U[4][4], UT[4][4];
-    get_mt(S0, h, c, X);          // L^-1 (M)
-    mprod<false>(X, X, Y, h, c);  // W = L^-T L^-1
-    get_mt(S1, h, c, X);          // C^-1 (M)
+    if constexpr (!Path::kModes) {
+      get_mt(S0, h, c, X);          // L^-1 (M)
+      mprod<false>(X, X, Y, h, c);  // W = L^-T L^-1
+    }
+    get_mt(S1, h, c, X);  // C^-1 (M)
     lds_fence();
-    put_m(S0, h, c, Y);            // W, row-major
-    put_rows<NN>(S1, t, i, bcol);  // rows of B^T
+    if constexpr (!Path::kModes) put_m(S0, h, c, Y);  // W, row-major
+    put_rows<NN>(S1, t, i, bcol);                     // rows of B^T
     lds_fence();
     get_mt(S1, h, c, Y);           // B (M)
     mprod<false>(X, Y, U, h, c);   // U = C^-T B
     mprod<false>(Y, X, UT, h, c);  // U^T = B^T C^-1
+    if constexpr (Path::kModes) {
+      get_m(S0, h, c, Y);           // L^-T (M): the A^T operand of L^-1 (.)
+      mprod<false>(Y, U, X, h, c);  // V = L^-1 U (M) -> the record, row-major
+#pragma unroll
+      for (int tt = 0; tt < 4; ++tt) {
+        const bool ok = grp * 4 + tt < npb;
+        double* rv = A.rrd + ((size_t)lc * npb + um[tt]) * NR;
+#pragma unroll
+        for (int q2 = 0; q2 < 4; ++q2) {
+          const int r = h + 4 * q2;
+          if (ok && r < NN && c < NN) rv[oV + r * NN + c] = X[tt][q2];
+        }
+      }
+      get_mt(S0, h, c, X);          // L^-1 (M)
+      mprod<false>(X, X, Y, h, c);  // W = L^-T L^-1
+      lds_fence();
+      put_m(S0, h, c, Y);  // W, row-major
+    }
     lds_fence();
     put_m(S1, h, c, UT);
     lds_fence();
@@ -481,7 +659,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
       const double tv = team_matvec<NN>(r_, w2);
       double den = fma(-kk, kk, r2);
       double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
-      if constexpr (SPHER) {
+      if constexpr (!Path::kSecant) {
         if (act && fabs(den) < kResClamp * r2) {
           st |= kStResonance;
           den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
@@ -515,24 +693,31 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
       get_rows<NN>(S0, t, i, r_);
       const double yy = team_matvec<NN>(r_, sd_i * mu_i * sv);
       double att;
-      if constexpr (SPHER) {
-        const double ct = P->chp[(size_t)lc * A.nsc + sl];
+      if constexpr (Path::kSpher) {
+        const double ct = P->chp[(size_t)lc * ns + sl];
         att = 0.5 * exp(-ct);
       } else {
-        // tauc null: sources for a unit beam at the layer top (the sweep scales them)
-        const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
+        // a flux path's tauc may be null: sources for a unit beam at the layer top (the
+        // sweep scales them)
+        const double tauc = (Path::kModes || A.tauc) ? A.tauc[(size_t)lc * ns + sl] : 0.0;
         att = 0.5 * exp(-tauc * rmu0);
       }
       const double dd = rg_i * fma(-yy, rmu0e, lxd);
       zp = (sv + dd) * att;
       zm = (sv - dd) * att;
-      if constexpr (SPHER) {  // a layer of zero depth leaves the diffuse field alone
-        e0 = taup > 0.0 ? exp(P->chp[(size_t)lc * A.nsc + sl] -
-                              P->chp[(size_t)(lc + 1) * A.nsc + sl])
+      if constexpr (Path::kSpher) {  // a layer of zero depth leaves the diffuse field alone
+        e0 = taup > 0.0 ? exp(P->chp[(size_t)lc * ns + sl] - P->chp[(size_t)(lc + 1) * ns + sl])
                         : 1.0;
       } else {
         e0 = exp(-taup * rmu0e);
       }
+    }
+    if constexpr (Path::kModes) {
+      if (wr) {
+        rr[oZp + i] = zp;
+        rr[oZm + i] = zm;
+      }
+      if (valid && i == 0) rr[oE0] = e0;
     }
     if (thin) {  // w = U Delta U^T x from the rows and columns of U^T in S1
       double r_[NN];
@@ -542,15 +727,16 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
       get_cols<NN>(S1, t, i, r_);
       wth = team_matvec<NN>(r_, yv * dq) * msk;
     }
+    // ---- Psi, Omega^T and the two Gram matrices ----
     get_m(S0, h, c, Y);            // W (M)
     mprod<false>(U, Y, X, h, c);   // U^T W
     // row scalings: Psi = Gamma^1/2 U^T W, Omega^T = Delta^1/2 U^T
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        X[tt][m] *= G[tt * 32 + 16 + h + 4 * m];
-        UT[tt][m] *= G[tt * 32 + h + 4 * m];
+      for (int q2 = 0; q2 < 4; ++q2) {
+        X[tt][q2] *= G[tt * 32 + 16 + h + 4 * q2];
+        UT[tt][q2] *= G[tt * 32 + h + 4 * q2];
       }
     mprod<true>(UT, UT, U, h, c);  // I + Omega Omega^T
     mprod<true>(X, X, Y, h, c);    // I + Psi^T Psi
@@ -587,6 +773,7 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
     lds_fence();
     get_rows<NN>(S0, t, i, hr);
     pv = ga0 - team_matvec<NN>(hr, ga);
+    // ---- A+ the same way from S1 ----
     get_rows<NN>(S1, t, i, hr);
     if (!team_chol<NN, false>(hr, unused, jrd)) st |= kStEigen;
     team_tri_inverse_col<NN>(hr, jrd, z);  // row i of K+^T
@@ -603,41 +790,54 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
   }
 
   // ---- store: R~ = A+ - A-, T~ = A- + A+ - I (M layout), S~+, S~-, tau' (T) ----
+  // a flux path: full rows, record ne1t; kModes: packed upper, record NE1 of rsw
 #pragma unroll
   for (int tt = 0; tt < 4; ++tt) {
     double chk = 0.0;
-    const bool ok = grp * 4 + tt < A.nsc;
-    const int slt = ok ? grp * 4 + tt : grp * 4, lct = lc;
-    double* rec = A.scr + ((size_t)lct * A.nsc + slt) * ne1t<NN>();
+    const bool ok = grp * 4 + tt < npb;
+    const int vt = um[tt];
 #pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const int r = h + 4 * m;
-      const double rr = Ap[tt][m] - Am[tt][m];
-      const double tr = (Am[tt][m] + Ap[tt][m]) - (r == c ? 1.0 : 0.0);
-      // whole 128-B rows per problem: nontemporal for a large chunk (hd_kernels.hpp);
-      // the team reads stay plain (8-byte pieces: with nt C5 ran 20 % slower)
-      if (ok && r < NN && c < NN) {
-        rec_st<NT>(&rec[r * NN + c], rr);
-        rec_st<NT>(&rec[NN * NN + r * NN + c], tr);
+    for (int q2 = 0; q2 < 4; ++q2) {
+      const int r = h + 4 * q2;
+      const double rrv = Ap[tt][q2] - Am[tt][q2];
+      const double trv = (Am[tt][q2] + Ap[tt][q2]) - (r == c ? 1.0 : 0.0);
+      if constexpr (Path::kModes) {
+        if (ok && r <= c && c < NN) {
+          const int e = sym_index<NN>(r, c);
+          out[(size_t)vt * NE1 + e] = rrv;
+          out[(size_t)vt * NE1 + nsym + e] = trv;
+        }
+      } else {
+        // whole 128-B rows per problem: nontemporal for a large chunk (hd_kernels.hpp);
+        // the team reads stay plain (8-byte pieces: with nt C5 ran 20 % slower)
+        double* rec = A.scr + ((size_t)lc * npb + vt) * ne1t<NN>();
+        if (ok && r < NN && c < NN) {
+          rec_st<Path::kNT>(&rec[r * NN + c], rrv);
+          rec_st<Path::kNT>(&rec[NN * NN + r * NN + c], trv);
+        }
       }
-      chk += rr + tr;
+      chk += rrv + trv;
     }
-    // this lane's share of problem tt's R~/T~: a non-finite entry flags problem tt
+    // this lane's share of problem tt's R~/T~: a non-finite entry flags problem tt's solve
     if (ok && !isfinite(chk)) {
-      atomicOr(&A.status[A.s0 + slt], kStNonFinite);
+      atomicOr(&A.status[A.s0 + (Path::kModes ? vt - (vt / ns) * ns : vt)], kStNonFinite);
       atomicOr(A.anyerr, 1);
     }
   }
   double chk = 0.0;
   const double sp = g_i * (zp * (1.0 - e0) - db) + pv - qv;
   const double sm = g_i * (-zm * (1.0 - e0) + db) - pv - qv;
-  double* rec = A.scr + ((size_t)lc * A.nsc + sl) * ne1t<NN>();
-  if (valid && act) {
-    rec[2 * NN * NN + ii] = sp;
-    rec[2 * NN * NN + NN + ii] = sm;
+  double* srec;  // S~+ | S~- | tau' of this team's record
+  if constexpr (Path::kModes)
+    srec = out + (size_t)u * NE1 + 2 * nsym;
+  else
+    srec = A.scr + ((size_t)lc * npb + sl) * ne1t<NN>() + 2 * NN * NN;
+  if (wr) {
+    srec[i] = sp;
+    srec[NN + i] = sm;
   }
   chk += sp + sm;
-  if (valid && i == 0) rec[2 * NN * NN + 2 * NN] = taup;
+  if (valid && i == 0) srec[2 * NN] = taup;
   if (act && !isfinite(chk + taup)) st |= kStNonFinite;
   if (valid && st) {
     atomicOr(&A.status[s], st);
@@ -647,13 +847,13 @@ __device__ __forceinline__ void team_mfma_layer_body(LayerArgs A, const SphArgs*
 template <int NN, bool NT>
 __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_kernel(LayerArgs A) {
   __shared__ double lds[2 * kSet + 4 * 2 * 16];
-  team_mfma_layer_body<NN, NT, false>(A, nullptr, lds);
+  team_layer_body<NN, FluxLayerPath<NT, false>>(A, nullptr, lds);
 }
 // hd_solve_spher / hd_solve_flx_spher: the team layer setup with the pseudo-spherical beam
 template <int NN, bool NT>
 __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_spher_kernel(LayerArgs A, SphArgs P) {
   __shared__ double lds[2 * kSet + 4 * 2 * 16];
-  team_mfma_layer_body<NN, NT, true>(A, &P, lds);
+  team_layer_body<NN, FluxLayerPath<NT, true>>(A, &P, lds);
 }
 
 // ============================================================================
@@ -1306,12 +1506,11 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArg
 
 // ============================================================================
 // Intensity path, nstr 18..32: hd_rad.hip's per-(unit, layer) setup
-// (hd_rad_layer_kernel: the flux layer setup for azimuthal mode m with the
-// Y_l^m(mu_i) tables, parity of l+m, beam source x (2 - delta_m0), thermal only
-// at m = 0, plus L, V, k, the particular solution and the exponentials kept for
-// the radiance kernels) on the team layout with the dense products on the matrix
-// core: hd_team_mfma_layer_kernel's algebra, four units per wave.  Writes the
-// radiance records unit-contiguous ([layer][unit][element]): rsw (R~/T~ packed
+// (hd_rad_layer_kernel) for four units (solve, azimuthal mode m) per wave:
+// team_layer_body on RadLayerPath -- the Y_l^m(mu_i) tables with the parity of
+// l+m, beam source x (2 - delta_m0), thermal only at m = 0, and L, V, k, the
+// particular solution and the exponentials kept for the radiance kernels.  Writes
+// the radiance records unit-contiguous ([layer][unit][element]): rsw (R~/T~ packed
 // upper, S~+-, tau') for the team sweep, rrd (L packed, V, k, Z+-, h, B_top,
 // dB/dtau', tau', omega', e^{-k tau'}, e^{-tau'/mu0}) for the team user-angle kernel
 // and the rolled flux / const / user kernels (hd_rad.hip's HD_RREC at these sizes).
@@ -1319,374 +1518,7 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArg
 template <int NN>
 __global__ __launch_bounds__(64, 2) void hd_rad_team_layer_kernel(RadArgs A) {
   __shared__ double lds[2 * kSet + 4 * 2 * 16];
-  double* S0 = lds;
-  double* S1 = lds + kSet;
-  double* G = lds + 2 * kSet;  // [t][dsq | gsq][16]
-  constexpr int N = 2 * NN;
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int NE1 = rad_layer_record_doubles(NN);
-  constexpr int NR = rad_rec_doubles(NN);
-  constexpr int oV = nsym, oK = nsym + NN * NN, oZp = oK + NN, oZm = oZp + NN, oH = oZm + NN;
-  constexpr int oBt = oH + NN, oSl = oBt + 1, oTp = oSl + 1, oOm = oTp + 1, oEk = oOm + 1;
-  constexpr int oE0 = oEk + NN;
-  const Quad<NN>& Qc = tquad<NN>(c_qt);
-  const int lane = (int)threadIdx.x;
-  const int h = lane >> 4, c = lane & 15;  // M layout
-  const int t = h, i = c;                  // T layout: team t, row i
-  const bool act = i < NN;
-  const int ii = act ? i : 0;
-  const int L = A.nlyr;
-  const size_t nu = A.nu;
-  // block = 4 consecutive units of one layer, blocks numbered layer-fastest and
-  // XCD-aware as in the flux kernel
-  const int grp = block_group(L);
-  const int lc = block_layer(L);
-  const bool valid = grp * 4 + t < A.nu;
-  const int u = valid ? grp * 4 + t : grp * 4;
-  const int m = u / A.ns;
-  const int sl = u - m * A.ns;
-  const long s = A.s0 + sl;
-  const int nm = A.nmom;
-  const int np = A.nprop;
-  const bool wr = valid && act;
-  int st = 0;
-  int um[4];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) um[tt] = grp * 4 + tt < A.nu ? grp * 4 + tt : grp * 4;
-  double* rr = A.rrd + ((size_t)lc * nu + u) * NR;   // element e: rr[e]
-  double* out = A.rsw + (size_t)lc * NE1 * nu;    // element e of unit v: out[v * NE1 + e]
-
-  for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;
-  lds_fence();
-
-  const double msk = act ? 1.0 : 0.0;
-  const double mu_i = fma(msk, Qc.mu[ii] - 1.0, 1.0);
-  const double sd_i = Qc.sd[ii] * msk;
-  const double g_i = Qc.g[ii] * msk;
-  const double rmu_i = Qc.rmu[ii] * msk;
-  const double rg_i = Qc.rg[ii] * msk;
-
-  // ---- inputs of this layer (harp layer L-1-lc) + delta-M (c_setdis) ----
-  const double* q = A.prop + ((size_t)s * L + (L - 1 - lc)) * np;
-  const double tau = q[0];
-  double ssa = np > 1 ? q[1] : 0.0;
-  if (!(tau >= 0.0) || !(ssa >= 0.0) || !(ssa <= 1.0)) st |= kStBadInput;
-  if (ssa == 1.0) ssa = 1.0 - kDither;
-  const double f = nm >= N ? q[1 + N] : 0.0;
-  if (!(f < 1.0)) st |= kStBadInput;
-  const double taup = (1.0 - ssa * f) * tau;
-  const double om = ssa * (1.0 - f) / (1.0 - ssa * f);
-  const double rf = om / (1.0 - f);
-
-  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
-  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
-  if (fb > 0.0 && !(mu0 > 0.0 && mu0 <= 1.0)) st |= kStBadInput;  // cdisort c_chekin
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
-  const double mub = beam ? mu0 : 0.0;
-  const bool therm = A.planck && m == 0;
-
-  // ---- mode-m phase-matrix rows (parity of l+m): S+ (ap), S- (lch); beam sums ----
-  double ap[NN], lch[NN];
-  double xs = 0.0, xd = 0.0;
-  sfor<0, NN>([&](auto J) { ap[HD_K(J)] = lch[HD_K(J)] = 0.0; });
-  {
-    const int mp = m & 1;
-    const double* lam = rad_lam<NN>(m);
-    const double sx = sqrt(fmax(0.0, 1.0 - mub * mub));
-    double seed = c_rtt.seed[m];
-    for (int a = 0; a < m; ++a) seed *= sx;  // Y_m^m(mu0)
-    double y1 = 0.0, y2 = 0.0;                // Y_{l-1}^m(mu0), Y_{l-2}^m(mu0)
-#pragma nounroll
-    for (int l2 = 0; l2 < NN; ++l2) {
-      const int la = 2 * l2, lb = la + 1;
-      const double ya =
-          la < m ? 0.0 : (la == m ? seed : fma(c_rtt.ra[m][la] * mub, y1, -c_rtt.rb[m][la] * y2));
-      y2 = y1;
-      y1 = ya;
-      const double yb =
-          lb < m ? 0.0 : (lb == m ? seed : fma(c_rtt.ra[m][lb] * mub, y1, -c_rtt.rb[m][lb] * y2));
-      y2 = y1;
-      y1 = yb;
-      const int le = mp ? lb : la, lo = mp ? la : lb;
-      const double pe0 = mp ? yb : ya, po0 = mp ? ya : yb;
-      const double che = le == 0 ? 1.0 : (le <= nm ? q[1 + le] : 0.0);
-      const double cho = lo == 0 ? 1.0 : (lo <= nm ? q[1 + lo] : 0.0);
-      const double ge = (2 * le + 1) * (che - f) * rf;
-      const double go = (2 * lo + 1) * (cho - f) * rf;
-      const double te = lam[le * NN + ii] * msk;  // Y_le^m(mu_i), this lane's node
-      const double to = lam[lo * NN + ii] * msk;
-      const double ue = ge * te;
-      const double uo = go * to;
-      xs = fma(ue, pe0, xs);
-      xd = fma(uo, po0, xd);
-      sfor<0, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        ap[j] = fma(ue, bc<j>(te), ap[j]);
-        lch[j] = fma(uo, bc<j>(to), lch[j]);
-      });
-    }
-  }
-  sfor<0, NN>([&](auto J) {
-    constexpr int j = HD_K(J);
-    const double diag = i == j ? rmu_i : 0.0;
-    const double sij = sd_i * Qc.sd[j];
-    lch[j] = fma(-sij, lch[j], diag);
-    ap[j] = fma(-sij, ap[j], diag);
-  });
-  // L L^T = S-
-  double lt[NN], rdl;
-  if (!team_chol<NN, true>(lch, lt, rdl)) st |= kStEigen;
-  {  // L, packed lower row-major: row i holds lch[k], k <= i.  Branch-free: the
-     // elements a lane does not own go to the sink.  Stores under a lane-dependent
-     // condition inside the unrolled loop cost 1 KB of spill at two waves per SIMD
-    double* lrow = rr + i * (i + 1) / 2;
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      double* dst = (wr && k <= i) ? &lrow[k] : A.sink + lane;
-      *dst = lch[k];
-    });
-  }
-
-  // ---- pre-Jacobi vectors (depend on L only) ----
-  double w2 = 0.0, lxd = 0.0;
-  const double fb2 = fb * ((m == 0 ? 0.5 : 1.0) / kPi);
-  if (beam) {
-    const double y = sd_i * (fb2 * xs);
-    double z = 0.0;  // z = L^T y
-    sfor<0, NN>([&](auto K) { z = fma(lt[HD_K(K)], bc<HD_K(K)>(y), z); });
-    const double yl = team_matvec<NN>(lch, z);  // L z
-    const double xdi = -fb2 * xd;
-    const double rv = fma(-yl, rg_i, xdi * rmu0 * rmu_i);
-    w2 = g_i * rv;
-    lxd = sd_i * xdi;
-    team_lsolve<NN>(lch, rdl, w2);
-    team_usolve<NN>(lt, rdl, w2);
-    team_lsolve<NN>(lch, rdl, lxd);
-    team_usolve<NN>(lt, rdl, lxd);
-  }
-  double cvec = 0.0, db = 0.0, bsum = 0.0;
-  if (therm) {
-    const double bt = A.planckv[(size_t)(L - lc) * A.ns + sl];
-    const double bb = taup > 0.0 ? A.planckv[(size_t)(L - lc - 1) * A.ns + sl] : bt;
-    db = bb - bt;
-    bsum = bt + bb;
-    const double b1 = taup > 0.0 ? 2.0 * db / taup : 0.0;
-    cvec = sd_i * mu_i;
-    team_lsolve<NN>(lch, rdl, cvec);
-    team_usolve<NN>(lt, rdl, cvec);
-    if (wr) rr[oH + i] = rg_i * cvec;
-    cvec = fma(b1 * rg_i, cvec, db) * msk;
-    if (valid && i == 0) {
-      rr[oBt] = bt;
-      rr[oSl] = 0.5 * b1;
-    }
-  } else {
-    if (wr) rr[oH + i] = 0.0;
-    if (valid && i == 0) {
-      rr[oBt] = 0.0;
-      rr[oSl] = 0.0;
-    }
-  }
-  if (valid && i == 0) {
-    rr[oTp] = taup;
-    rr[oOm] = om;
-  }
-  {
-    double z[NN];
-    team_tri_inverse_col<NN>(lch, rdl, z);  // row i of L^-T -> S0 (lch dies here)
-    put_rows<NN>(S0, t, i, z);
-  }
-
-  // ---- C C^T = S+ ; B0 = C^T L (lane j: column j) ; C^-1 to LDS ----
-  double bcol[NN];
-  {
-    double unused[NN], rdc;
-    if (!team_chol<NN, false>(ap, unused, rdc)) st |= kStEigen;
-    sfor<0, NN>([&](auto I) {
-      constexpr int r = HD_K(I);
-      double uu = 0.0;
-      sfor<r, NN>([&](auto K) { uu = fma(bc<HD_K(K)>(ap[r]), lt[HD_K(K)], uu); });
-      bcol[r] = uu;
-      pin<NN>(ap);
-    });
-    double z[NN];
-    team_tri_inverse_col<NN>(ap, rdc, z);  // row i of C^-T -> S1
-    put_rows<NN>(S1, t, i, z);
-  }
-
-  // ---- eigenpairs: Sym = L^T S+ L = B0^T B0 = V diag(k^2) V^T ----
-  lds_fence();
-  if (!team_jacobi<NN>(bcol, A.max_sweeps)) st |= kStEigen;
-  lds_fence();
-  double kk;
-  {
-    double k2 = 0.0;
-    sfor<0, NN>([&](auto K) { k2 = fma(bcol[HD_K(K)], bcol[HD_K(K)], k2); });
-    if (act && !(k2 > 0.0)) st |= kStEigen;
-    kk = sqrt(k2 > 0.0 ? k2 : 0.0) * msk;
-    const double x = kk * taup;
-    const double mm = -expm1(-x);
-    const double th = mm * rcp_nr(2.0 - mm);
-    const double delta = x > 1.0e-8 ? th * rcp_nr(kk > 0.0 ? kk : 1.0) : 0.5 * taup;
-    G[t * 32 + i] = sqrt(delta) * msk;
-    G[t * 32 + 16 + i] = sqrt(kk * th) * msk;
-    if (wr) {
-      rr[oK + i] = kk;
-      rr[oEk + i] = 1.0 - mm;  // exp(-k tau')
-    }
-  }
-
-  // ---- the dense products on the matrix core; V = L^-1 U; the beam solution ----
-  double zp = 0.0, zm = 0.0, e0 = 0.0;
-  {
-    double X[4][4], Y[4][4], U[4][4], UT[4][4];
-    {
-      // L^-T stays in S0 until V = L^-1 U is formed; W = L^-T L^-1 is formed after
-      // it from the same rows (no M-layout copy of L^-T or W held across the products)
-      get_mt(S1, h, c, X);           // C^-1 (M)
-      lds_fence();
-      put_rows<NN>(S1, t, i, bcol);  // rows of B^T
-      lds_fence();
-      get_mt(S1, h, c, Y);           // B (M)
-      mprod<false>(X, Y, U, h, c);   // U = C^-T B
-      mprod<false>(Y, X, UT, h, c);  // U^T = B^T C^-1
-      get_m(S0, h, c, Y);            // L^-T (M): the A^T operand of L^-1 (.)
-      mprod<false>(Y, U, X, h, c);   // V = L^-1 U (M) -> the record, row-major
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        const bool ok = grp * 4 + tt < A.nu;
-        double* rv = A.rrd + ((size_t)lc * nu + um[tt]) * NR;
-#pragma unroll
-        for (int q2 = 0; q2 < 4; ++q2) {
-          const int r = h + 4 * q2;
-          if (ok && r < NN && c < NN) rv[oV + r * NN + c] = X[tt][q2];
-        }
-      }
-      get_mt(S0, h, c, X);          // L^-1 (M)
-      mprod<false>(X, X, Y, h, c);  // W = L^-T L^-1
-      lds_fence();
-      put_m(S0, h, c, Y);           // W, row-major
-    }
-    lds_fence();
-    put_m(S1, h, c, UT);
-    lds_fence();
-    if (beam) {
-      double r_[NN];
-      get_rows<NN>(S1, t, i, r_);
-      const double r2 = rmu0 * rmu0;
-      const double tv = team_matvec<NN>(r_, w2);
-      double den = fma(-kk, kk, r2);
-      if (act && fabs(den) < kResClamp * r2) {
-        st |= kStResonance;
-        den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
-      }
-      const double ttv = tv / den * msk;
-      get_cols<NN>(S1, t, i, r_);
-      const double sv = team_matvec<NN>(r_, ttv) * rg_i;
-      get_rows<NN>(S0, t, i, r_);
-      const double yy = team_matvec<NN>(r_, sd_i * mu_i * sv);
-      const double tauc = A.tauc[(size_t)lc * A.ns + sl];
-      const double att = 0.5 * exp(-tauc * rmu0);
-      const double dd = rg_i * fma(-yy, rmu0, lxd);
-      zp = (sv + dd) * att;
-      zm = (sv - dd) * att;
-      e0 = exp(-taup * rmu0);
-    }
-    if (wr) {
-      rr[oZp + i] = zp;
-      rr[oZm + i] = zm;
-    }
-    if (valid && i == 0) rr[oE0] = e0;
-    get_m(S0, h, c, Y);            // W (M)
-    mprod<false>(U, Y, X, h, c);   // U^T W
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-      for (int q2 = 0; q2 < 4; ++q2) {
-        X[tt][q2] *= G[tt * 32 + 16 + h + 4 * q2];
-        UT[tt][q2] *= G[tt * 32 + h + 4 * q2];
-      }
-    mprod<true>(UT, UT, U, h, c);  // I + Omega Omega^T
-    mprod<true>(X, X, Y, h, c);    // I + Psi^T Psi
-    lds_fence();
-    put_m(S0, h, c, U);
-    put_m(S1, h, c, Y);
-    lds_fence();
-  }
-  const double ga = g_i * (cvec - fma(-zp, e0, zm));
-  const double gb = g_i * (fma(zp, e0, zm) + bsum);
-
-  // ---- A- = (I + Omega Omega^T)^-1, A+ = (I + Psi^T Psi)^-1 ----
-  double Am[4][4], Ap[4][4];
-  double pv, qv;
-  {
-    double hr[NN], unused[NN], z[NN], jrd, X[4][4];
-    get_rows<NN>(S0, t, i, hr);
-    if (!team_chol<NN, false>(hr, unused, jrd)) st |= kStEigen;
-    team_tri_inverse_col<NN>(hr, jrd, z);
-    lds_fence();
-    put_rows<NN>(S0, t, i, z);
-    lds_fence();
-    get_mt(S0, h, c, X);
-    mprod<false>(X, X, Am, h, c);
-    lds_fence();
-    put_m(S0, h, c, Am);
-    lds_fence();
-    get_rows<NN>(S0, t, i, hr);
-    pv = ga - team_matvec<NN>(hr, ga);
-    get_rows<NN>(S1, t, i, hr);
-    if (!team_chol<NN, false>(hr, unused, jrd)) st |= kStEigen;
-    team_tri_inverse_col<NN>(hr, jrd, z);
-    lds_fence();
-    put_rows<NN>(S1, t, i, z);
-    lds_fence();
-    get_mt(S1, h, c, X);
-    mprod<false>(X, X, Ap, h, c);
-    lds_fence();
-    put_m(S1, h, c, Ap);
-    lds_fence();
-    get_rows<NN>(S1, t, i, hr);
-    qv = team_matvec<NN>(hr, gb) - gb;
-  }
-
-  // ---- store: R~ = A+ - A-, T~ = A- + A+ - I packed upper (M layout), S~+-, tau' ----
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) {
-    double chk = 0.0;
-    const bool ok = grp * 4 + tt < A.nu;
-#pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2) {
-      const int r = h + 4 * q2;
-      const double rrv = Ap[tt][q2] - Am[tt][q2];
-      const double trv = (Am[tt][q2] + Ap[tt][q2]) - (r == c ? 1.0 : 0.0);
-      if (ok && r <= c && c < NN) {
-        const int e = sym_index<NN>(r, c);
-        out[(size_t)um[tt] * NE1 + e] = rrv;
-        out[(size_t)um[tt] * NE1 + nsym + e] = trv;
-      }
-      chk += rrv + trv;
-    }
-    if (ok && !isfinite(chk)) {
-      const int vt = um[tt];
-      atomicOr(&A.status[A.s0 + (vt - (vt / A.ns) * A.ns)], kStNonFinite);
-      atomicOr(A.anyerr, 1);
-    }
-  }
-  double chk = 0.0;
-  const double sp = g_i * (zp * (1.0 - e0) - db) + pv - qv;
-  const double sm = g_i * (-zm * (1.0 - e0) + db) - pv - qv;
-  if (wr) {
-    out[(size_t)u * NE1 + 2 * nsym + i] = sp;
-    out[(size_t)u * NE1 + 2 * nsym + NN + i] = sm;
-  }
-  chk += sp + sm;
-  if (valid && i == 0) out[(size_t)u * NE1 + 2 * nsym + 2 * NN] = taup;
-  if (act && !isfinite(chk + taup)) st |= kStNonFinite;
-  if (valid && st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
+  team_layer_body<NN, RadLayerPath>(A, nullptr, lds);
 }
 
 // ============================================================================

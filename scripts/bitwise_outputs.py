@@ -154,6 +154,22 @@ def dump(out_dir):
         save(f"rays_band_n{nstr}",
              d.forward_rays_band(*a, umu=t(umu), phi=t(phi), weights=t([0.7, 1.9])))
 
+    # ---- radiances on the team path (nstr 18..32) with a Planck source: with a beam (every
+    # azimuthal mode) and without (one mode); units = modes x nwave x ncol, the last a count
+    # that is no multiple of the four units of a team block (54), as is the beamless one (6)
+    for nstr, beam, nwave in ((18, 1, 2), (32, 1, 2), (18, 0, 2), (18, 1, 1)):
+        rng = np.random.default_rng(7000 + 10 * nstr + 2 * beam + nwave)
+        ncol, nlyr = 3, 6
+        prop, bc, temf = _inputs(rng, nwave, ncol, nlyr, nstr, 1, beam)
+        prop[..., 0] = rng.uniform(0.3, 1.0, prop.shape[:3])  # every user depth inside
+        d = disort(nstr, nlyr, nwave, ncol, 1, flags="lamber,quiet,usrtau,usrang", user_tau=utau,
+                   user_mu=[-1.0, -0.6, -0.15, 0.1, 0.45, 0.8], user_phi=[0.0, 75.0, 300.0])
+        st = torch.zeros(nwave * ncol, dtype=torch.int32, device=dev)
+        tag = f"n{nstr}_p1_b{beam}_w{nwave}"
+        save("radflux_" + tag, d.forward(t(prop), tb(bc), t(temf), status=st))
+        save("get_rad_" + tag, d.get_rad())
+        save("radstatus_" + tag, st)
+
     # ---- Beer-Lambert
     rng = np.random.default_rng(555)
     nstr, nlyr, nwave, ncol = 8, 17, 5, 11

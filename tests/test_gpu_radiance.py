@@ -221,6 +221,68 @@ def test_radiance_chunking_invariance():
     assert np.array_equal(f1, f2) and np.array_equal(u1, u2)
 
 
+_PARTIAL = {}
+
+
+def _partial_block_case(nstr):
+    """nwave 1, ncol 3, nlyr 3 on the team path, solved once with the automatic chunking
+    and once one solve a chunk; shared by the two tests below.  With a beam the units are
+    3 * nstr = 54 (nstr 18) and 90 (nstr 30): two units in the last block of four.  nstr 32
+    has no fbeam key, so one mode and 3 units: one block whose fourth team is past the end."""
+    if nstr in _PARTIAL:
+        return _PARTIAL[nstr]
+    from pyharp_amd.disort import _context
+    rng = np.random.default_rng(1800 + nstr)
+    nwave, ncol, nlyr = 1, 3, 3
+    prop, bc, kw = _random_case(rng, nwave, ncol, nlyr, nstr, True)
+    if nstr == 32:
+        del bc["fbeam"]
+    total = prop[..., 0].sum(axis=-1).min()
+    utau = np.sort(np.concatenate([[0.0, total], rng.uniform(0, total, 3)]))
+    umu = [-1.0, -0.6, -0.15, 0.1, 0.45, 0.8]
+    phi = [0.0, 75.0, 180.0, 300.0]
+    d = _disort(nstr, nlyr, nwave, ncol, flags="usrtau,usrang,lamber,quiet", umu=umu, phi=phi,
+                utau=utau, planck=True, wl=kw["wave_lower"], wu=kw["wave_upper"])
+    p, t = torch.as_tensor(prop, device=DEV), torch.as_tensor(kw["temf"], device=DEV)
+    runs = []
+    ctx = _context(0)
+    for chunk in (0, 1):
+        st = torch.full((nwave * ncol,), -1, dtype=torch.int32, device=DEV)
+        ctx.set_chunk(chunk)
+        try:
+            flux = d.forward(p, _dev(bc), t, status=st).cpu().numpy()
+            runs.append((flux, d.get_rad().cpu().numpy(), st.cpu().numpy()))
+        finally:
+            ctx.set_chunk(0)
+    ref = disort_rad_forward(prop, bc, kw["temf"], nstr=nstr, umu=umu, phi=phi, utau=utau,
+                             planck=True, wave_lower=kw["wave_lower"],
+                             wave_upper=kw["wave_upper"])
+    _PARTIAL[nstr] = (runs, ref)
+    return _PARTIAL[nstr]
+
+
+@pytest.mark.parametrize("nstr", [18, 30, 32])
+def test_team_partial_block_vs_oracle(nstr):
+    """hd_rad_team_layer_kernel's last block of four units partly past the end (the unit
+    count no multiple of 4): radiances, fluxes and status against the oracle"""
+    (run, _), (fref, uref) = _partial_block_case(nstr)
+    flux, uu, st = run
+    assert uu.shape == uref.shape
+    assert margin(_col_err(uu, uref)) < TOL, _col_err(uu, uref)
+    assert margin(rel_err(flux, fref).max()) < TOL
+    assert np.all(st == 0), st
+
+
+@pytest.mark.parametrize("nstr", [18, 30, 32])
+def test_team_partial_block_chunking_invariance(nstr):
+    """the same calls one solve a chunk (nstr 18, 30: every chunk ends in a partial block)
+    equal the automatic chunking bitwise"""
+    (a, b), _ = _partial_block_case(nstr)
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y)
+    assert np.all(b[2] == 0), b[2]
+
+
 def test_radiance_argument_errors():
     with pytest.raises(RuntimeError):
         _disort(34, 2, 1, 1, flags="usrang,lamber", umu=[0.5], phi=[0.0])
