@@ -408,9 +408,7 @@ HD_UNROLL_NN
     }
     const double gam = (g0 + g1) * (sg[p] * sg[q]);
     const double app = nrm[p], aqq = nrm[q];
-    const double g2 = gam * gam;
-    off += g2;
-    const bool rot = on && g2 > 1.0e-30 * (app * aqq);
+    off = fma(gam, gam, off);
     const double d = aqq - app;
     double t;
     if constexpr (HD_JACOBI_F32_ANGLE && !F64) {
@@ -418,13 +416,26 @@ HD_UNROLL_NN
       // c = 1/sqrt(1 + t^2) in FP64, so the rotation is orthogonal to FP64 rounding
       // whatever t is: an angle good to ~1e-7 only leaves ~1e-7 of g behind, which
       // the next sweep removes (quadratic convergence until off ~ 1e-7 of the
-      // diagonal; the stop rule sits at 1e-8)
+      // diagonal; the stop rule sits at 1e-8).
+      // Every pair of a lane that is still on rotates: a coupling below 1e-15 of its
+      // columns gives |t| <~ 1e-15, a rotation by rounding error, where a relative skip
+      // test cost two FP64 MULs, a compare and the selects per rotation (DESIGN.md
+      // section 5).  A lane that is off gets t = 0 exactly through the numerator; the
+      // denominator is floored at the smallest normal float, so d = g = 0 (two columns
+      // with no coupling and equal norms, or both flushed to zero in FP32) gives
+      // 0 * finite = 0 and never 0 * inf
       const float df = (float)d, g2f = 2.0f * (float)gam;
       const float wf = __builtin_amdgcn_sqrtf(__builtin_fmaf(g2f, g2f, df * df));
-      const float tf = (df < 0.0f ? -g2f : g2f) * __builtin_amdgcn_rcpf(__builtin_fabsf(df) + wf);
-      t = rot ? (double)tf : 0.0;
+      const float dn = __builtin_fmaxf(__builtin_fabsf(df) + wf, 1.17549435e-38f);
+      // sgn(d) 2 g: d's sign bit flips g's (two integer ops, no compare and select)
+      const float sn = __builtin_bit_cast(
+          float, __builtin_bit_cast(unsigned, g2f) ^ (__builtin_bit_cast(unsigned, df) & 0x80000000u));
+      const float nu = on ? sn : 0.0f;
+      t = (double)(nu * __builtin_amdgcn_rcpf(dn));
     } else {
       // w = sqrt(d^2 + 4 g^2): t = sgn(d) 2 g / (|d| + w)
+      const double g2 = gam * gam;
+      const bool rot = on && g2 > 1.0e-30 * (app * aqq);
       const double w2 = rot ? fma(d, d, 4.0 * g2) : 1.0;
       const double w = w2 * rsq_nr(w2);
       t = rot ? (d < 0.0 ? -2.0 : 2.0) * gam * rcp_nr(fabs(d) + w) : 0.0;
@@ -506,11 +517,12 @@ HD_UNROLL_NN
 // by 1/mu0^2 - k^2: within 3e-4 of that resonance the layer kernels polish
 // (profiles/r06/resonance.txt: a C4 layer at 2.3e-6 of it gave 8.7e-7 in the fluxes
 // without the polish, 3e-9 with FP64 angles).  No-op for the other lanes; the wave
-// skips it when no lane needs it.
+// skips it when no lane needs it.  Returns true (for the whole wave) when the sweep
+// ran: column norms taken before it are then stale.
 template <int NN>
-__device__ __forceinline__ void jacobi_os_polish(double (&b)[NN][NN], bool need) {
+__device__ __forceinline__ bool jacobi_os_polish(double (&b)[NN][NN], bool need) {
   if constexpr (NN > 1) {
-    if (!__any(need)) return;
+    if (!__any(need)) return false;
     constexpr int P = NN + (NN & 1);
     double sg[NN], rs[NN], nrm[NN], off = 0.0;
 HD_UNROLL_NN
@@ -527,21 +539,30 @@ HD_UNROLL_NN
     for (int j = 0; j < NN; ++j)
 HD_UNROLL_NN
       for (int i = 0; i < NN; ++i) b[i][j] *= sg[j];
+    return true;
+  }
+  return false;
+}
+
+// the eigenvalues k_j^2 = |b_j|^2 of the rotated B
+template <int NN>
+__device__ __forceinline__ void column_norms2(const double (&b)[NN][NN], double (&k2)[NN]) {
+HD_UNROLL_NN
+  for (int j = 0; j < NN; ++j) {
+    double t = 0.0;
+HD_UNROLL_NN
+    for (int i = 0; i < NN; ++i) t = fma(b[i][j], b[i][j], t);
+    k2[j] = t;
   }
 }
 
-// true when some eigenvalue k^2 = |b_j|^2 of the rotated B lies within `tol` (relative)
-// of the beam resonance k^2 = r2 = 1/mu0^2
+// true when some eigenvalue k2[j] lies within `tol` (relative) of the beam resonance
+// k^2 = r2 = 1/mu0^2
 template <int NN>
-__device__ __forceinline__ bool near_resonance(const double (&b)[NN][NN], double r2, double tol) {
+__device__ __forceinline__ bool near_resonance(const double (&k2)[NN], double r2, double tol) {
   bool near = false;
 HD_UNROLL_NN
-  for (int j = 0; j < NN; ++j) {
-    double k2 = 0.0;
-HD_UNROLL_NN
-    for (int i = 0; i < NN; ++i) k2 = fma(b[i][j], b[i][j], k2);
-    near = near || fabs(r2 - k2) < tol * r2;
-  }
+  for (int j = 0; j < NN; ++j) near = near || fabs(r2 - k2[j]) < tol * r2;
   return near;
 }
 

@@ -47,6 +47,37 @@ __constant__ QuadTables c_quad;
 // hd_solve_flx: h = g / mu of every NN (row NN-1), the mean-intensity functional
 // sum_i w_i I_i = sum_i h_i psi_i -- a table of its own, so that Quad keeps its layout
 __constant__ double c_quad_h[kMaxRegNN][kMaxRegNN];
+// The layer kernel's Legendre tables with the basis scale folded in, likewise tables of
+// their own (the team and radiance kernels share Quad): spt[l][i] = sd_i P_l(mu_i), so
+// that -A+ and -A- accumulate as diag - sum_l g_l spt[l][i] spt[l][j] with no scaling pass
+// after the loop, and rmusd_i = 1 / (mu_i sd_i) for the beam source that arrives scaled
+template <int NN>
+struct QuadS {
+  double spt[2 * NN][NN];
+  double rmusd[NN];
+};
+struct QuadSTables {
+  QuadS<1> q1;
+  QuadS<2> q2;
+  QuadS<3> q3;
+  QuadS<4> q4;
+  QuadS<5> q5;
+  QuadS<6> q6;
+  QuadS<7> q7;
+  QuadS<8> q8;
+};
+__constant__ QuadSTables c_quad_s;
+template <int NN>
+__device__ __forceinline__ const QuadS<NN>& quad_s() {
+  if constexpr (NN == 1) return c_quad_s.q1;
+  else if constexpr (NN == 2) return c_quad_s.q2;
+  else if constexpr (NN == 3) return c_quad_s.q3;
+  else if constexpr (NN == 4) return c_quad_s.q4;
+  else if constexpr (NN == 5) return c_quad_s.q5;
+  else if constexpr (NN == 6) return c_quad_s.q6;
+  else if constexpr (NN == 7) return c_quad_s.q7;
+  else return c_quad_s.q8;
+}
 // 1/n for the beam's Legendre recursion (uniform index: scalar loads)
 __constant__ double c_inv_int[2 * kMaxRegNN + 2] = {
     0.0,        1.0,        1.0 / 2,  1.0 / 3,  1.0 / 4,  1.0 / 5,  1.0 / 6,
@@ -333,12 +364,16 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   // ---- phase matrix even/odd parts (-A+ in ap, -A- in lch, upper) and the
   //      beam source vectors; one even/odd Legendre pair per iteration so the
   //      constant tables stream through a few scalar registers ----
+  //      The tables carry the basis scale (spt[l][i] = sd_i P_l(mu_i)) and the
+  //      coefficients their sign, so the accumulators start at diag(1/mu) and end as
+  //      -A+ and -A-; xs and xd end as -sd_i times the beam sums
+  const QuadS<NN>& Qs = quad_s<NN>();
   double lch[NN][NN], ap[NN][NN], xs[NN], xd[NN];
 #pragma unroll
   for (int i = 0; i < NN; ++i) {
     xs[i] = xd[i] = 0.0;
 #pragma unroll
-    for (int j = i; j < NN; ++j) lch[i][j] = ap[i][j] = 0.0;
+    for (int j = i; j < NN; ++j) lch[i][j] = ap[i][j] = (i == j) ? Qc.rmu[i] : 0.0;
   }
   {
     double pprev = 0.0, pcur = 1.0;  // P_{l-1}(mu0), P_l(mu0) for the beam
@@ -347,8 +382,8 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
       const int le = 2 * l2, lo = le + 1;
       const double che = le == 0 ? 1.0 : (le <= nm ? q[1 + le] : 0.0);
       const double cho = lo <= nm ? q[1 + lo] : 0.0;
-      const double ge = (2 * le + 1) * (che - f) * rf;
-      const double go = (2 * lo + 1) * (cho - f) * rf;
+      const double ge = -(2 * le + 1) * (che - f) * rf;
+      const double go = -(2 * lo + 1) * (cho - f) * rf;
       const double pe0 = pcur;  // P_le(mu0)
       const double po0 = ((2 * lo - 1) * mub * pcur - (lo - 1) * pprev) * c_inv_int[lo];
       pprev = po0;
@@ -356,8 +391,8 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
       double ue[NN], uo[NN];
 #pragma unroll
       for (int i = 0; i < NN; ++i) {
-        ue[i] = ge * Qc.pt[le][i];
-        uo[i] = go * Qc.pt[lo][i];
+        ue[i] = ge * Qs.spt[le][i];
+        uo[i] = go * Qs.spt[lo][i];
         xs[i] = fma(ue[i], pe0, xs[i]);
         xd[i] = fma(uo[i], po0, xd[i]);
       }
@@ -365,20 +400,11 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
       for (int i = 0; i < NN; ++i)
 #pragma unroll
         for (int j = i; j < NN; ++j) {
-          ap[i][j] = fma(ue[i], Qc.pt[le][j], ap[i][j]);
-          lch[i][j] = fma(uo[i], Qc.pt[lo][j], lch[i][j]);
+          ap[i][j] = fma(ue[i], Qs.spt[le][j], ap[i][j]);
+          lch[i][j] = fma(uo[i], Qs.spt[lo][j], lch[i][j]);
         }
     }
   }
-#pragma unroll
-  for (int i = 0; i < NN; ++i)
-#pragma unroll
-    for (int j = i; j < NN; ++j) {
-      const double diag = (i == j) ? Qc.rmu[i] : 0.0;
-      const double sij = Qc.sd[i] * Qc.sd[j];
-      lch[i][j] = fma(-sij, lch[i][j], diag);
-      ap[i][j] = fma(-sij, ap[i][j], diag);
-    }
   // L L^T = -A-  (lower triangle of lch)
   double rdl[NN];
   if (!chol_inplace<NN>(lch, rdl)) st |= kStEigen;
@@ -391,7 +417,7 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   if (beam) {
     double y[NN], z[NN];
 #pragma unroll
-    for (int i = 0; i < NN; ++i) y[i] = Qc.sd[i] * (fb2 * xs[i]);
+    for (int i = 0; i < NN; ++i) y[i] = -fb2 * xs[i];  // D^1/2 (fb2 xs): xs holds -sd xs
 #pragma unroll
     for (int i = 0; i < NN; ++i) {  // z = L^T y
       double t = 0.0;
@@ -408,11 +434,12 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
     }
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
-      // rv = (-y/sd + xd/mu0)/mu, with 1/(sd mu) = 1/g; W D^-1/2 = diag(w/sd) = diag(g)
-      const double xdi = -fb2 * xd[i];
-      const double rv = fma(-y[i], Qc.rg[i], xdi * rmu0 * Qc.rmu[i]);
+      // rv = (-y/sd + xd/mu0)/mu, with 1/(sd mu) = 1/g; W D^-1/2 = diag(w/sd) = diag(g).
+      // xd holds -sd xd, so D^1/2 (-fb2 xd) = fb2 xd[i], and rv takes it over mu sd
+      const double sxd = fb2 * xd[i];
+      const double rv = fma(-y[i], Qc.rg[i], sxd * rmu0 * Qs.rmusd[i]);
       y2[i] = Qc.g[i] * rv;
-      lxd[i] = Qc.sd[i] * xdi;
+      lxd[i] = sxd;
     }
     lower_solve<NN>(lch, rdl, y2);    // V^T y2 below (V = B K^-1 after the Jacobi)
     lower_solve<NN>(lch, rdl, lxd);   // lxd = L^-T L^-1 D^1/2 xd
@@ -495,17 +522,19 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
 #endif
   HD_PHASE();
   if (!jacobi_os<NN>(v, A.max_sweeps)) st |= kStEigen;
-  jacobi_os_polish<NN>(v, beam && near_resonance<NN>(v, rmu0 * rmu0, kResPolish));
+  // k_j^2 = |b_j|^2, formed once: the resonance test reads it, and only a wave that
+  // polished (rare) forms it again from the polished columns
+  double k2[NN];
+  column_norms2<NN>(v, k2);
+  if (jacobi_os_polish<NN>(v, beam && near_resonance<NN>(k2, rmu0 * rmu0, kResPolish)))
+    column_norms2<NN>(v, k2);
   HD_PHASE();
   double kk[NN], rk[NN];  // k_j = |b_j|, 1/k_j
 #pragma unroll
   for (int j = 0; j < NN; ++j) {
-    double k2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < NN; ++i) k2 = fma(v[i][j], v[i][j], k2);
-    if (!(k2 > 0.0)) st |= kStEigen;
-    const double r = k2 > 0.0 ? rsq_nr(k2) : 0.0;
-    kk[j] = k2 * r;
+    if (!(k2[j] > 0.0)) st |= kStEigen;
+    const double r = k2[j] > 0.0 ? rsq_nr(k2[j]) : 0.0;
+    kk[j] = k2[j] * r;
     rk[j] = r;
   }
   // beam, the part that needs only B and k (before L is back: y2 dies first)
@@ -790,15 +819,10 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   for (int i = 0; i < NN; ++i) out.put(RL::Sm + i, smv[i]);
   out.close(RL::Sm + NN - 1);
   out.put(RL::Tau, taup);
-  // the pad after tau': the layer's direct-beam transmission e^(-tau'/mu0) (1
-  // without a beam; the beam's own transmission, not the one of a secant moved off
-  // a resonance).  No kernel reads it any more -- its one reader was the LDS-state
-  // nstr-16 sweep -- and dropping the store is a change to this
-  // kernel's code, left for a change that is measured
-  if constexpr (!SPHER) {
-    if (rmu0e != rmu0) e0 = exp(-taup * rmu0);
-  }
-  out.put(RL::Tau + 1, beam ? e0 : 1.0);
+  // the pad after tau' goes out as zero: no kernel reads it (its one reader, the
+  // LDS-state nstr-16 sweep of DESIGN.md section 9, took the layer's direct-beam
+  // transmission from it)
+  out.close(RL::Tau);
   if (!isfinite(chk + taup)) st |= kStNonFinite;
   return st;
 }
@@ -1860,6 +1884,14 @@ void warm_eigvecs(int nn, const QuadHost& q, int ia, int ib, double* vout) {
     for (int j = 0; j < nn; ++j) vout[i * nn + j] = (double)v[i][j];
 }
 
+template <int NN>
+static void fill_quad_s(QuadS<NN>& q, const QuadHost& h) {
+  for (int i = 0; i < NN; ++i) {
+    q.rmusd[i] = 1.0 / (h.mu[i] * h.sd[i]);
+    for (int l = 0; l < 2 * NN; ++l) q.spt[l][i] = h.sd[i] * h.pt[l][i];
+  }
+}
+
 hipError_t upload_quad_tables(const QuadHost* per_nn /* [kMaxNN], index nn-1 */) {
   QuadTables t;
   fill_quad<1>(t.q1, per_nn[0]);
@@ -1874,6 +1906,17 @@ hipError_t upload_quad_tables(const QuadHost* per_nn /* [kMaxNN], index nn-1 */)
   for (int nn = 1; nn <= kMaxRegNN; ++nn)
     for (int i = 0; i < nn; ++i) h[nn - 1][i] = per_nn[nn - 1].g[i] / per_nn[nn - 1].mu[i];
   hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_quad_h), h, sizeof(h), 0, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return e;
+  QuadSTables s;
+  fill_quad_s<1>(s.q1, per_nn[0]);
+  fill_quad_s<2>(s.q2, per_nn[1]);
+  fill_quad_s<3>(s.q3, per_nn[2]);
+  fill_quad_s<4>(s.q4, per_nn[3]);
+  fill_quad_s<5>(s.q5, per_nn[4]);
+  fill_quad_s<6>(s.q6, per_nn[5]);
+  fill_quad_s<7>(s.q7, per_nn[6]);
+  fill_quad_s<8>(s.q8, per_nn[7]);
+  e = hipMemcpyToSymbol(HIP_SYMBOL(c_quad_s), &s, sizeof(s), 0, hipMemcpyHostToDevice);
   if (e != hipSuccess) return e;
   return hipMemcpyToSymbol(HIP_SYMBOL(c_quad), &t, sizeof(t), 0, hipMemcpyHostToDevice);
 }

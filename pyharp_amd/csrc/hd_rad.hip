@@ -419,13 +419,13 @@ HD_RUNROLL
       v[i][j] = t;
     }
   if (!jacobi_os<NN>(v, A.max_sweeps)) st |= kStEigen;
-  jacobi_os_polish<NN>(v, beam && near_resonance<NN>(v, rmu0 * rmu0, kResPolish));
-  double kk[NN];
+  double kk[NN];  // k_j^2 first (hd_layer_kernel's form), then k_j
+  column_norms2<NN>(v, kk);
+  if (jacobi_os_polish<NN>(v, beam && near_resonance<NN>(kk, rmu0 * rmu0, kResPolish)))
+    column_norms2<NN>(v, kk);
 HD_RUNROLL
   for (int j = 0; j < NN; ++j) {
-    double k2 = 0.0;
-HD_RUNROLL
-    for (int i = 0; i < NN; ++i) k2 = fma(v[i][j], v[i][j], k2);
+    const double k2 = kk[j];
     if (!(k2 > 0.0)) st |= kStEigen;
     const double rk = k2 > 0.0 ? rsq_nr(k2) : 0.0;
     kk[j] = k2 * rk;

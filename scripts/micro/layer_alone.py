@@ -45,5 +45,5 @@ for _ in range(5):
     swp.append(tm.sweep_ms)
 lay.sort()
 swp.sort()
-print(f"{sys.argv[1] if len(sys.argv) > 1 else 'cur'} (max sweeps {sweeps or 'default'}): layer alone {lay[2]:.3f} ms (min {lay[0]:.3f}), "
+print(f"{sys.argv[1] if len(sys.argv) > 1 else 'cur'} (max sweeps {sweeps or 'default'}): layer alone {lay[2]:.3f} ms (min {lay[0]:.3f}, max {lay[4]:.3f}), "
       f"sweep+backsub {swp[2]:.3f} ms, checksum {float(out.sum()):.12e}")
