@@ -655,12 +655,22 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   // ---- layer operators in the flux-weighted basis ----
   // Delta = tanh(k tau'/2)/k, Gamma = k tanh(k tau'/2): Gamma^1/2 K^-1 = Delta^1/2
   double dsq[NN];
+  double kt[NN], em[NN];  // k tau', 1 - exp(-k tau')
+#pragma unroll
+  for (int j = 0; j < NN; ++j) kt[j] = kk[j] * taup;
+  hd_m_expm1_neg_n<NN>(kt, em);
+  // the empty asm keeps the NN evaluations together and unconditional: without it each
+  // is sunk into a branch of its own under the x > 1e-8 test below, with every constant
+  // of the series formed again in vector registers
+#pragma unroll
+  for (int j = 0; j < NN; ++j) asm volatile("" : "+v"(em[j]));
 #pragma unroll
   for (int j = 0; j < NN; ++j) {
-    const double x = kk[j] * taup;
-    const double m = -expm1(-x);           // 1 - exp(-k tau')
+    const double x = kt[j];
+    const double m = em[j];
     const double th = m * rcp_nr(2.0 - m);  // tanh(k tau'/2)
-    const double delta = x > 1.0e-8 ? th * rcp_nr(kk[j] > 0.0 ? kk[j] : 1.0) : 0.5 * taup;
+    // 1/k_j is rk[j] already (x > 1e-8 implies k_j > 0)
+    const double delta = x > 1.0e-8 ? th * rk[j] : 0.5 * taup;
     dsq[j] = delta > 0.0 ? delta * rsq_nr1(delta) : 0.0;
   }
   // Psi^T = L^-T V Gamma^1/2 = L^-T B Delta^1/2 -> LDS (one column per step)
@@ -1058,19 +1068,15 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
       bp.close(RB::Ch);
     }
     HD_PHASE();
-    // A = Ra (full); W1 = I - R_l A ; v1 = R_l Sd + S+
-    double am[NN][NN], w1[NN][NN], t1[NN];
-#pragma unroll
-    for (int i = 0; i < NN; ++i)
-#pragma unroll
-      for (int j = 0; j < NN; ++j) am[i][j] = HD_SYM(ra, i, j);
+    // A = Ra (read through its upper triangle); W1 = I - R_l A ; v1 = R_l Sd + S+
+    double w1[NN][NN], t1[NN];
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
 #pragma unroll
       for (int j = 0; j < NN; ++j) {
         double t = (i == j) ? 1.0 : 0.0;
 #pragma unroll
-        for (int k = 0; k < NN; ++k) t = fma(-HD_SYM(rl, i, k), am[k][j], t);
+        for (int k = 0; k < NN; ++k) t = fma(-HD_SYM(rl, i, k), HD_SYM(ra, k, j), t);
         w1[i][j] = t;
       }
       double t = spl[i];
@@ -1112,28 +1118,33 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
     for (int i = 0; i < NN; ++i) {
       double t = sd[i];
 #pragma unroll
-      for (int k = 0; k < NN; ++k) t = fma(am[i][k], t1[k], t);
+      for (int k = 0; k < NN; ++k) t = fma(HD_SYM(ra, i, k), t1[k], t);
       u[i] = t;
       bp.put(RB::Tv + i, t1[i]);
     }
     bp.close(RB::Tv + NN - 1);
     HD_PHASE();
-    // M1 = A W1^-1, row-wise in place:  x W1 = a  ->  (x L) U = a
+    // M1 = A W1^-1 = A (I - R_l A)^-1 is symmetric with A and R_l ((I - A R_l) A =
+    // A (I - R_l A)), so only its upper triangle is formed and kept: row r of
+    // x W1 = a  ->  (x L) U = a, the backward substitution stopping at column r
+    double m1[NN][NN];
 #pragma unroll
     for (int r = 0; r < NN; ++r) {
+      double z[NN];
 #pragma unroll
       for (int j = 0; j < NN; ++j) {  // z U = a  (forward over columns)
-        double t = am[r][j];
+        double t = HD_SYM(ra, r, j);
 #pragma unroll
-        for (int k = 0; k < j; ++k) t = fma(-am[r][k], w1[k][j], t);
-        am[r][j] = t * w1[j][j];
+        for (int k = 0; k < j; ++k) t = fma(-z[k], w1[k][j], t);
+        z[j] = t * w1[j][j];
       }
 #pragma unroll
-      for (int j = NN - 1; j >= 0; --j) {  // x L = z  (backward, unit L)
-        double t = am[r][j];
+      for (int j = NN - 1; j >= r; --j) {  // x L = z  (backward, unit L)
+        double t = z[j];
 #pragma unroll
-        for (int k = j + 1; k < NN; ++k) t = fma(-am[r][k], w1[k][j], t);
-        am[r][j] = t;
+        for (int k = j + 1; k < NN; ++k) t = fma(-z[k], w1[k][j], t);
+        z[j] = t;
+        m1[r][j] = t;
       }
     }
     HD_PHASE();
@@ -1184,30 +1195,51 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
     }
     bp.close(RB::Z + NN * NN - 1);
     HD_PHASE();
-    // P = M1 T_l (row-wise in place)
-#pragma unroll
-    for (int r = 0; r < NN; ++r) {
-      double row[NN];
+    // P = M1 T_l and Ra <- R_l + T_l P (upper).  NN > 4: one column of both at a time --
+    // column j of Ra needs column j of P only, so P is never held whole.  NN <= 4, where
+    // everything fits the vector registers: P whole, then Ra (the column form cost three
+    // nstr-6 spher instantiations a wave per SIMD of occupancy)
+    if constexpr (NN > 4) {
 #pragma unroll
       for (int j = 0; j < NN; ++j) {
-        double t = 0.0;
+        double pc[NN];
 #pragma unroll
-        for (int k = 0; k < NN; ++k) t = fma(am[r][k], HD_SYM(tl, k, j), t);
-        row[j] = t;
+        for (int r = 0; r < NN; ++r) {
+          double t = 0.0;
+#pragma unroll
+          for (int k = 0; k < NN; ++k) t = fma(HD_SYM(m1, r, k), HD_SYM(tl, k, j), t);
+          pc[r] = t;
+        }
+#pragma unroll
+        for (int i = 0; i <= j; ++i) {
+          double t = rl[i][j];
+#pragma unroll
+          for (int k = 0; k < NN; ++k) t = fma(HD_SYM(tl, i, k), pc[k], t);
+          ra[i][j] = t;
+        }
       }
+    } else {
+      double pm[NN][NN];
 #pragma unroll
-      for (int j = 0; j < NN; ++j) am[r][j] = row[j];
-    }
-    HD_PHASE();
-    // Ra <- R_l + T_l P (upper)
+      for (int r = 0; r < NN; ++r) {
 #pragma unroll
-    for (int i = 0; i < NN; ++i) {
+        for (int j = 0; j < NN; ++j) {
+          double t = 0.0;
 #pragma unroll
-      for (int j = i; j < NN; ++j) {
-        double t = rl[i][j];
+          for (int k = 0; k < NN; ++k) t = fma(HD_SYM(m1, r, k), HD_SYM(tl, k, j), t);
+          pm[r][j] = t;
+        }
+      }
+      HD_PHASE();
 #pragma unroll
-        for (int k = 0; k < NN; ++k) t = fma(HD_SYM(tl, i, k), am[k][j], t);
-        ra[i][j] = t;
+      for (int i = 0; i < NN; ++i) {
+#pragma unroll
+        for (int j = i; j < NN; ++j) {
+          double t = rl[i][j];
+#pragma unroll
+          for (int k = 0; k < NN; ++k) t = fma(HD_SYM(tl, i, k), pm[k][j], t);
+          ra[i][j] = t;
+        }
       }
     }
   }
