@@ -12,10 +12,6 @@
 namespace hd {
 
 template <int NN>
-__host__ __device__ constexpr int ne1() {  // per-layer operator record (doubles)
-  return NN * (NN + 1) + 2 * NN + 1;
-}
-template <int NN>
 __host__ __device__ constexpr int ne2() {  // per-level back-substitution record
   return NN * NN + 2 * NN + 1;
 }

@@ -1,34 +1,23 @@
-// hd_rad.hpp -- argument block and launchers of the intensity path
-// (hd_rad.hip): every azimuthal mode, user optical depths and user angles,
-// nstr <= 32 (one lane per (solve, mode) problem).
+// hd_rad.hpp -- argument block and launchers of the intensity path: every
+// azimuthal mode, user optical depths and user angles, nstr <= 32.  A unit is one
+// (solve, mode) problem.  Which kernel exists in which form:
+//   hd_rad.hip       the kernels without NN (taus, azimuth, tms, ray, ray cosines);
+//                    nstr <= 16 only, NN-loops unrolled, one lane per unit: layer,
+//                    sweep, user_map; the chunk's launch sequence for every nstr
+//   hd_rad_lane.hpp  const and flux, one lane per problem at every nstr: unrolled in
+//                    hd_rad.hip (NN 1..8), rolled in hd_rad_wide.hip (hd::wide, NN 9..16)
+//   hd_rad_wide.hip  nstr 18..32 only, rolled: user (HD_RAD_USER=rolled, per-column
+//                    rays, more user angles than the team kernel takes)
+//   hd_team_mfma.hip nstr 18..32 only, four units per wave: layer, sweep, user
+// The records these kernels exchange are laid out in hd_rad_layout.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "hd_kernels.hpp"
+#include "hd_rad_layout.hpp"  // the records, their addressing, the Y_l^m table fill
 
 namespace hd {
-
-constexpr int kRadMaxNN = kMaxNN;  // nstr <= 32 (NN > 8: rolled loops, private memory)
-
-template <int NN>
-__host__ __device__ constexpr int rad_nsym() {
-  return NN * (NN + 1) / 2;
-}
-// per-(unit, layer) layer-operator record of the intensity kernels: the register
-// path's layout (R~, T~ upper, S~+, S~-, tau') at every nstr
-__host__ __device__ constexpr int rad_layer_record_doubles(int nn) {
-  return nn * (nn + 1) + 2 * nn + 1;
-}
-// per-(unit, layer) radiance record: L (packed lower), V, k, Z+, Z-, h, B_top,
-// dB/dtau', tau', omega', exp(-k tau'), exp(-tau'/mu0)
-__host__ __device__ constexpr int rad_rec_doubles(int nn) {
-  return nn * (nn + 1) / 2 + nn * nn + 5 * nn + 5;
-}
-// per-(unit, layer) sweep record for the back-substitution: ZT, t, R_above (packed), S_down
-__host__ __device__ constexpr int rad_bsub_doubles(int nn) {
-  return nn * nn + 2 * nn + nn * (nn + 1) / 2;
-}
 
 struct RadArgs {
   // inputs (per solve, index s = s0 + sl)
@@ -46,12 +35,13 @@ struct RadArgs {
   const double* phi;   // [nphi] degrees
   const double* utau;  // [ntau] unscaled, ascending; null = the nlyr+1 levels
   // scratch (unit u = m*ns + sl is the fastest index)
-  double* rsw;   // [nlyr][ne1][nu]   layer operators (flux-kernel layout); nstr > 16:
-                 //   [nlyr][nu][ne1] (team kernels, unit-contiguous)
-  double* rrd;   // [nlyr][rad_rec][nu]; nstr > 16: [nlyr][nu][rad_rec]
-  double* bsub;  // [nlyr][rad_bsub][nu]; nstr > 16: [nlyr][nu][rad_bsub]
-  double* lev;   // [nlyr+1][2NN][nu]   I+ (NN) then I- (NN) per level, solver order
-  double* cst;   // [nlyr][2NN][nu]     C+ then C-
+  // records and their addressing: hd_rad_layout.hpp
+  double* rsw;   // [nlyr][RadOps][nu]   layer operators; nstr > 16: [nlyr][nu][RadOps]
+                 //   (team kernels, unit-contiguous)
+  double* rrd;   // [nlyr][RadRec][nu]; nstr > 16: [nlyr][nu][RadRec]
+  double* bsub;  // [nlyr][RadBsub][nu]; nstr > 16: [nlyr][nu][RadBsub]
+  double* lev;   // [nlyr+1][RadLev][nu]  I+ (NN) then I- (NN) per level, solver order
+  double* cst;   // [nlyr][RadCst][nu]    C+ then C-
   double* radm;  // [ntau*numu][nu]     radiance per mode
   // outputs
   double* flux;  // [S][ntau][2], index 0 = deepest user depth
@@ -139,6 +129,32 @@ __device__ __forceinline__ double user_mu(const RadArgs& A, long s, int iu) {
   return A.umu[user_angle(A, s, iu)];
 }
 
+// The one-lane kernels' tables, one object in constant memory per translation unit: the
+// quadrature and the Y_l^m table of every NN in [LO, HI]; rad_tabs<NN>(c) is NN's pair
+template <int LO, int HI>
+struct RadTabs {
+  Quad<LO> q;
+  RadTab<LO> t;
+  RadTabs<LO + 1, HI> next;
+};
+template <int HI>
+struct RadTabs<HI, HI> {
+  Quad<HI> q;
+  RadTab<HI> t;
+};
+template <int NN, int LO, int HI>
+__host__ __device__ __forceinline__ const RadTabs<NN, HI>& rad_tabs(const RadTabs<LO, HI>& c) {
+  if constexpr (NN == LO) return c;
+  else return rad_tabs<NN>(c.next);
+}
+// host: fills the tables from the host quadratures (index nn-1)
+template <int LO, int HI>
+inline void fill_rad(RadTabs<LO, HI>& c, const QuadHost* per_nn) {
+  fill_quad(c.q, per_nn[LO - 1]);
+  fill_rad_tables(LO, per_nn[LO - 1].mu, &c.t.lam[0][0][0]);
+  if constexpr (LO < HI) fill_rad(c.next, per_nn);
+}
+
 hipError_t upload_rad_tables(const QuadHost* per_nn);  // nn 1..kRadMaxNN
 // tauc/planck prologue must have run (launch_prologue) for the chunk's solves;
 // radiances = false: fluxes at the user depths only (mode 0, no uu)
@@ -160,10 +176,14 @@ hipError_t launch_rad_team_layer(int nn, const RadArgs& a, hipStream_t stream);
 // the layer-operator records, free after the sweep)
 hipError_t launch_rad_team_user(int nn, const RadArgs& a, hipStream_t stream);
 hipError_t upload_rad_tables_team(const QuadHost* per_nn);
-// nstr 18..32: the same kernels compiled with rolled NN-loops (hd_rad_wide.hip)
+// nstr 18..32: the one-lane kernels with rolled NN-loops (hd_rad_wide.hip) -- the
+// layers' homogeneous constants (a.nm modes), the fluxes at the user depths, the
+// per-(unit, angle) user-angle integration -- and their tables
 namespace wide {
 hipError_t upload_rad_tables(const QuadHost* per_nn);
-hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_t stream);
+hipError_t launch_rad_const(int nn, const RadArgs& a, hipStream_t stream);
+hipError_t launch_rad_flux(int nn, const RadArgs& a, hipStream_t stream);
+hipError_t launch_rad_user(int nn, const RadArgs& a, hipStream_t stream);
 }  // namespace wide
 
 }  // namespace hd

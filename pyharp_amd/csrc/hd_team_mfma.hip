@@ -154,23 +154,17 @@ __device__ __forceinline__ int block_layer(int L) { return block_logical() % L; 
 
 // Y_l^m(mu_i) tables of nstr 18..32 for the intensity path's team kernels (mode
 // m, degree l < nstr, node i) and the Y_l^m recurrence coefficients; filled
-// from the same host recurrence as hd_rad.hip's tables (upload_rad_tables_team)
-template <int NN>
-struct RadTabTeam {
-  double lam[2 * NN][2 * NN][NN];
-};
+// by fill_rad_tables (hd_rad_layout.hpp) as hd_rad.hip's tables (upload_rad_tables_team)
 struct RadTabsTeam {
-  RadTabTeam<9> t9;
-  RadTabTeam<10> t10;
-  RadTabTeam<11> t11;
-  RadTabTeam<12> t12;
-  RadTabTeam<13> t13;
-  RadTabTeam<14> t14;
-  RadTabTeam<15> t15;
-  RadTabTeam<16> t16;
-  double seed[2 * kMaxNN];               // prod_{a<=m} sqrt((2a-1)/(2a))
-  double ra[2 * kMaxNN][2 * kMaxNN];     // (2l-1)/sqrt(l^2-m^2), l > m
-  double rb[2 * kMaxNN][2 * kMaxNN];     // sqrt((l-1)^2-m^2)/sqrt(l^2-m^2), l > m
+  RadTab<9> t9;
+  RadTab<10> t10;
+  RadTab<11> t11;
+  RadTab<12> t12;
+  RadTab<13> t13;
+  RadTab<14> t14;
+  RadTab<15> t15;
+  RadTab<16> t16;
+  RadCoef co;  // seed, ra, rb
 };
 __constant__ RadTabsTeam c_rtt;
 
@@ -305,18 +299,18 @@ __device__ __forceinline__ void phase_rows_mode(const double* q, int nm, double 
   const int mp = m & 1;
   const double* lam = rad_lam<NN>(m);
   const double sx = sqrt(fmax(0.0, 1.0 - mub * mub));
-  double seed = c_rtt.seed[m];
+  double seed = c_rtt.co.seed[m];
   for (int a = 0; a < m; ++a) seed *= sx;  // Y_m^m(mu0)
   double y1 = 0.0, y2 = 0.0;                // Y_{l-1}^m(mu0), Y_{l-2}^m(mu0)
 #pragma nounroll
   for (int l2 = 0; l2 < NN; ++l2) {
     const int la = 2 * l2, lb = la + 1;
     const double ya =
-        la < m ? 0.0 : (la == m ? seed : fma(c_rtt.ra[m][la] * mub, y1, -c_rtt.rb[m][la] * y2));
+        la < m ? 0.0 : (la == m ? seed : fma(c_rtt.co.ra[m][la] * mub, y1, -c_rtt.co.rb[m][la] * y2));
     y2 = y1;
     y1 = ya;
     const double yb =
-        lb < m ? 0.0 : (lb == m ? seed : fma(c_rtt.ra[m][lb] * mub, y1, -c_rtt.rb[m][lb] * y2));
+        lb < m ? 0.0 : (lb == m ? seed : fma(c_rtt.co.ra[m][lb] * mub, y1, -c_rtt.co.rb[m][lb] * y2));
     y2 = y1;
     y1 = yb;
     const int le = mp ? lb : la, lo = mp ? la : lb;
@@ -355,13 +349,10 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
   double* S1 = lds + kSet;
   double* G = lds + 2 * kSet;  // [t][dsq | gsq][16]
   constexpr int N = 2 * NN;
-  // the records of a kModes path: rsw (NE1 doubles a unit) and rrd (NR, offsets o*)
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int NE1 = rad_layer_record_doubles(NN);
-  constexpr int NR = rad_rec_doubles(NN);
-  constexpr int oV = nsym, oK = nsym + NN * NN, oZp = oK + NN, oZm = oZp + NN, oH = oZm + NN;
-  constexpr int oBt = oH + NN, oSl = oBt + 1, oTp = oSl + 1, oOm = oTp + 1, oEk = oOm + 1;
-  constexpr int oE0 = oEk + NN;
+  // the records of a kModes path: rsw (RadOps, NE1 doubles a unit) and rrd (RadRec, NR)
+  using R = RadRec<NN>;
+  constexpr int NE1 = RadOps<NN>::size;
+  constexpr int NR = R::size;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
   const int lane = (int)threadIdx.x;
   const int h = lane >> 4, c = lane & 15;  // M layout
@@ -497,27 +488,27 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
     team_lsolve<NN>(lch, rdl, cvec);
     team_usolve<NN>(lt, rdl, cvec);
     if constexpr (Path::kModes) {
-      if (wr) rr[oH + i] = rg_i * cvec;  // h
+      if (wr) rr[R::H + i] = rg_i * cvec;  // h
     }
     // a thin layer keeps the slope part 2 (dB/tau') h alone here: Q~- takes it below
     cvec = fma(b1 * rg_i, cvec, thin ? 0.0 : db) * msk;
     if constexpr (Path::kModes) {
       if (valid && i == 0) {
-        rr[oBt] = bt;
-        rr[oSl] = 0.5 * b1;
+        rr[R::Bt] = bt;
+        rr[R::Sl] = 0.5 * b1;
       }
     }
   } else if constexpr (Path::kModes) {
-    if (wr) rr[oH + i] = 0.0;
+    if (wr) rr[R::H + i] = 0.0;
     if (valid && i == 0) {
-      rr[oBt] = 0.0;
-      rr[oSl] = 0.0;
+      rr[R::Bt] = 0.0;
+      rr[R::Sl] = 0.0;
     }
   }
   if constexpr (Path::kModes) {
     if (valid && i == 0) {
-      rr[oTp] = taup;
-      rr[oOm] = om;
+      rr[R::Tp] = taup;
+      rr[R::Om] = om;
     }
   }
   {
@@ -600,8 +591,8 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
     G[t * 32 + 16 + i] = sqrt(kk * th) * msk;
     if constexpr (Path::kModes) {
       if (wr) {
-        rr[oK + i] = kk;
-        rr[oEk + i] = 1.0 - mm;  // exp(-k tau')
+        rr[R::K + i] = kk;
+        rr[R::Ek + i] = 1.0 - mm;  // exp(-k tau')
       }
     }
   }
@@ -639,7 +630,7 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
 #pragma unroll
         for (int q2 = 0; q2 < 4; ++q2) {
           const int r = h + 4 * q2;
-          if (ok && r < NN && c < NN) rv[oV + r * NN + c] = X[tt][q2];
+          if (ok && r < NN && c < NN) rv[R::V + r * NN + c] = X[tt][q2];
         }
       }
       get_mt(S0, h, c, X);          // L^-1 (M)
@@ -714,10 +705,10 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
     }
     if constexpr (Path::kModes) {
       if (wr) {
-        rr[oZp + i] = zp;
-        rr[oZm + i] = zm;
+        rr[R::Zp + i] = zp;
+        rr[R::Zm + i] = zm;
       }
-      if (valid && i == 0) rr[oE0] = e0;
+      if (valid && i == 0) rr[R::E0] = e0;
     }
     if (thin) {  // w = U Delta U^T x from the rows and columns of U^T in S1
       double r_[NN];
@@ -804,8 +795,8 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
       if constexpr (Path::kModes) {
         if (ok && r <= c && c < NN) {
           const int e = sym_index<NN>(r, c);
-          out[(size_t)vt * NE1 + e] = rrv;
-          out[(size_t)vt * NE1 + nsym + e] = trv;
+          out[(size_t)vt * NE1 + RadOps<NN>::R + e] = rrv;
+          out[(size_t)vt * NE1 + RadOps<NN>::T + e] = trv;
         }
       } else {
         // whole 128-B rows per problem: nontemporal for a large chunk (hd_kernels.hpp);
@@ -829,7 +820,7 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
   const double sm = g_i * (-zm * (1.0 - e0) + db) - pv - qv;
   double* srec;  // S~+ | S~- | tau' of this team's record
   if constexpr (Path::kModes)
-    srec = out + (size_t)u * NE1 + 2 * nsym;
+    srec = out + (size_t)u * NE1 + RadOps<NN>::Sp;
   else
     srec = A.scr + ((size_t)lc * npb + sl) * ne1t<NN>() + 2 * NN * NN;
   if (wr) {
@@ -1513,7 +1504,7 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArg
 // the radiance records unit-contiguous ([layer][unit][element]): rsw (R~/T~ packed
 // upper, S~+-, tau') for the team sweep, rrd (L packed, V, k, Z+-, h, B_top,
 // dB/dtau', tau', omega', e^{-k tau'}, e^{-tau'/mu0}) for the team user-angle kernel
-// and the rolled flux / const / user kernels (hd_rad.hip's HD_RREC at these sizes).
+// and the rolled flux / const / user kernels (RadUnitMajor, hd_rad_layout.hpp).
 // ============================================================================
 template <int NN>
 __global__ __launch_bounds__(64, 2) void hd_rad_team_layer_kernel(RadArgs A) {
@@ -1540,9 +1531,10 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
   double* S0 = lds;
   double* S1 = lds + kSet;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int NE1 = rad_layer_record_doubles(NN);
-  constexpr int NB = rad_bsub_doubles(NN);
+  using O = RadOps<NN>;
+  using B = RadBsub<NN>;
+  constexpr int NE1 = O::size;
+  constexpr int NB = B::size;
   const int lane = (int)threadIdx.x;
   const int h = lane >> 4, c = lane & 15;  // M layout
   const int t = h, i = c;                  // T layout: team t, row i
@@ -1601,13 +1593,13 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
     double* bp = A.bsub + (size_t)lc * NB * nu;
     // the stack above this layer: R_above (packed upper, row i from j = i) and S_down
     {  // branch-free: the elements a lane does not own go to the sink
-      double* urow = bp + (size_t)u * NB + NN * NN + NN + sym_index<NN>(ii, ii) - ii;
+      double* urow = bp + (size_t)u * NB + B::Ra + sym_index<NN>(ii, ii) - ii;
       sfor<0, NN>([&](auto J) {
         constexpr int j = HD_K(J);
         double* dst = (wr && j >= i) ? urow + j : A.sink + lane;
         *dst = ra[j];
       });
-      *(wr ? bp + (size_t)u * NB + NN * NN + NN + nsym + i : A.sink + lane) = sd;
+      *(wr ? bp + (size_t)u * NB + B::Sd + i : A.sink + lane) = sd;
     }
     // R~, T~ (packed upper) of the four units in M layout; this unit's rows (T layout)
     double rm[4][4], tm[4][4];
@@ -1618,17 +1610,17 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
         const int r = h + 4 * q;
         const bool in = r < NN && c < NN;
         const int e = in ? sym_index<NN>(r, c) : 0;
-        rm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + e] : 0.0;
-        tm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + nsym + e] : 0.0;
+        rm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + O::R + e] : 0.0;
+        tm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + O::T + e] : 0.0;
       }
     double rl[NN], tr[NN];
     sfor<0, NN>([&](auto J) {
       const int e = sym_index<NN>(ii, HD_K(J));
-      rl[HD_K(J)] = lp[(size_t)u * NE1 + e] * msk;
-      tr[HD_K(J)] = lp[(size_t)u * NE1 + nsym + e] * msk;
+      rl[HD_K(J)] = lp[(size_t)u * NE1 + O::R + e] * msk;
+      tr[HD_K(J)] = lp[(size_t)u * NE1 + O::T + e] * msk;
     });
-    const double spl = lp[(size_t)u * NE1 + 2 * nsym + ii] * msk;
-    const double sml = lp[(size_t)u * NE1 + 2 * nsym + NN + ii] * msk;
+    const double spl = lp[(size_t)u * NE1 + O::Sp + ii] * msk;
+    const double sml = lp[(size_t)u * NE1 + O::Sm + ii] * msk;
     // W1 = I - R A on the matrix core, to team rows through LDS
     {
       double pw[4][4];
@@ -1676,7 +1668,7 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
     // u = A t1 + Sd
     double uv = sd;
     sfor<0, NN>([&](auto K) { uv = fma(ra[HD_K(K)], bc<HD_K(K)>(t1), uv); });
-    *(wr ? bp + (size_t)u * NB + NN * NN + i : A.sink + lane) = t1;
+    *(wr ? bp + (size_t)u * NB + B::Tv + i : A.sink + lane) = t1;
     // ZT = W1^-1 T = U^-1 (L^-1 T): columns of the triangular inverses on the team
     // (lane i: row i of the transposed inverse), the products on the matrix core
     {
@@ -1723,7 +1715,7 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
         for (int q = 0; q < 4; ++q) {
           const int r = h + 4 * q;
           const bool own = ok && r < NN && c < NN;
-          *(own ? bp + (size_t)um[tt] * NB + r * NN + c : A.sink + lane) = zm[tt][q];
+          *(own ? bp + (size_t)um[tt] * NB + B::Z + r * NN + c : A.sink + lane) = zm[tt][q];
         }
       }
       mprod<false>(ram, zm, pm, h, c);  // A ZT
@@ -1738,7 +1730,7 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
     }
     get_rows<NN>(S0, t, i, ra);
     sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
-    tauc += lp[(size_t)u * NE1 + 2 * nsym + 2 * NN];
+    tauc += lp[(size_t)u * NE1 + O::Tau];
   }
 
   // ---- Lambertian surface (mode 0): I+ = g x ----
@@ -1754,30 +1746,30 @@ __global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
   {
     double dn = sd;
     sfor<0, NN>([&](auto J) { dn = fma(ra[HD_K(J)], bc<HD_K(J)>(ip), dn); });
-    double* lv = A.lev + (size_t)L * 2 * NN * nu;
+    double* lv = A.lev + (size_t)L * RadLev<NN>::size * nu;
     if (wr) {
-      lv[(size_t)i * nu + u] = x;
-      lv[(size_t)(NN + i) * nu + u] = dn * rg_i;
+      lv[(size_t)(RadLev<NN>::Ip + i) * nu + u] = x;
+      lv[(size_t)(RadLev<NN>::Im + i) * nu + u] = dn * rg_i;
     }
     chk += dn * msk;
   }
   // ---- back-substitution bottom -> top, I+ and I- at every level ----
   for (int lc = L - 1; lc >= 0; --lc) {
     const double* bp = A.bsub + (size_t)lc * NB * nu;
-    double nip = bp[(size_t)u * NB + NN * NN + ii] * msk;
+    double nip = bp[(size_t)u * NB + B::Tv + ii] * msk;
     sfor<0, NN>([&](auto J) {
-      nip = fma(bp[(size_t)u * NB + ii * NN + HD_K(J)] * msk, bc<HD_K(J)>(ip), nip);
+      nip = fma(bp[(size_t)u * NB + B::Z + ii * NN + HD_K(J)] * msk, bc<HD_K(J)>(ip), nip);
     });
     ip = nip;
-    double dn = bp[(size_t)u * NB + NN * NN + NN + nsym + ii] * msk;
+    double dn = bp[(size_t)u * NB + B::Sd + ii] * msk;
     sfor<0, NN>([&](auto J) {
-      const double r = bp[(size_t)u * NB + NN * NN + NN + sym_index<NN>(ii, HD_K(J))] * msk;
+      const double r = bp[(size_t)u * NB + B::Ra + sym_index<NN>(ii, HD_K(J))] * msk;
       dn = fma(r, bc<HD_K(J)>(ip), dn);
     });
-    double* lv = A.lev + (size_t)lc * 2 * NN * nu;
+    double* lv = A.lev + (size_t)lc * RadLev<NN>::size * nu;
     if (wr) {
-      lv[(size_t)i * nu + u] = ip * rg_i;
-      lv[(size_t)(NN + i) * nu + u] = dn * rg_i;
+      lv[(size_t)(RadLev<NN>::Ip + i) * nu + u] = ip * rg_i;
+      lv[(size_t)(RadLev<NN>::Im + i) * nu + u] = dn * rg_i;
     }
     chk += ip + dn;
   }
@@ -1934,12 +1926,9 @@ void hd_rad_team_user_kernel(RadArgs A) {
   __shared__ double lds[kSet + 8 * 32 + 8 * 4 + 8 * 8];
   double* S0 = lds;          // rows of L^-T
   constexpr int N = 2 * NN;
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int NE1 = rad_layer_record_doubles(NN);
-  constexpr int NR = rad_rec_doubles(NN);
-  constexpr int oV = nsym, oK = nsym + NN * NN, oZp = oK + NN, oZm = oZp + NN, oH = oZm + NN;
-  constexpr int oBt = oH + NN, oSl = oBt + 1, oTp = oSl + 1, oOm = oTp + 1, oEk = oOm + 1;
-  constexpr int oE0 = oEk + NN;
+  using R = RadRec<NN>;
+  constexpr int NE1 = RadOps<NN>::size;
+  constexpr int NR = R::size;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
   const int lane = (int)threadIdx.x;
   const int h = lane >> 4, c = lane & 15;  // M layout
@@ -1990,7 +1979,7 @@ void hd_rad_team_user_kernel(RadArgs A) {
     const double om = ssa * (1.0 - f) / (1.0 - ssa * f);
     ft[tt] = f;
     rft[tt] = om / (1.0 - f);
-    taupt[tt] = rv(oTp, tt);
+    taupt[tt] = rv(R::Tp, tt);
   }
   double* red = lds + kSet;      // [angle][lay | sc | x0 | th][h, parity]
   double* aux = red + 8 * 32;     // [angle][ab | a0 | a1t | -]
@@ -2041,7 +2030,7 @@ void hd_rad_team_user_kernel(RadArgs A) {
         for (int q = 0; q < 4; ++q) {
           const int r = h + 4 * q;
           const bool in = r < NN && c < NN;
-          vm[q] = in ? rl(oV + (in ? r * NN + c : 0), tt) : 0.0;
+          vm[q] = in ? rl(R::V + (in ? r * NN + c : 0), tt) : 0.0;
         }
         d4 p = {0.0, 0.0, 0.0, 0.0}, gq = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -2065,19 +2054,19 @@ void hd_rad_team_user_kernel(RadArgs A) {
           const int side = c & 1;
           const double tsd = side ? taup : 0.0;
           const double ebs = exp(-tsd * rmu0);
-          const double bt = rl(oBt, tt), slope = rl(oSl, tt);
+          const double bt = rl(R::Bt, tt), slope = rl(R::Sl, tt);
           const double b2 = 2.0 * fma(slope, tsd, bt);
-          const double* lv = A.lev + (size_t)(lc + side) * 2 * NN * nu + uml[tt];
+          const double* lv = A.lev + (size_t)(lc + side) * RadLev<NN>::size * nu + uml[tt];
           double bx[4], by[4];
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
             const int r = h + 4 * s4;
             const bool in = r < NN && c < 4;
             const int rr_ = in ? r : 0;
-            const double ipl = in ? lv[(size_t)rr_ * nu] : 0.0;
-            const double imi = in ? lv[(size_t)(NN + rr_) * nu] : 0.0;
-            const double zp = in ? rl(oZp + rr_, tt) : 0.0, zm = in ? rl(oZm + rr_, tt) : 0.0;
-            const double hr = in ? rl(oH + rr_, tt) : 0.0;
+            const double ipl = in ? lv[(size_t)(RadLev<NN>::Ip + rr_) * nu] : 0.0;
+            const double imi = in ? lv[(size_t)(RadLev<NN>::Im + rr_) * nu] : 0.0;
+            const double zp = in ? rl(R::Zp + rr_, tt) : 0.0, zm = in ? rl(R::Zm + rr_, tt) : 0.0;
+            const double hr = in ? rl(R::H + rr_, tt) : 0.0;
             const double gr = Qc.g[rr_];
             bx[s4] = (in && c < 2) ? gr * (ipl + imi - (zp + zm) * ebs - b2) : 0.0;
             by[s4] = (in && c >= 2) ? gr * (ipl - imi - (zp - zm) * ebs - 2.0 * slope * hr) : 0.0;
@@ -2090,16 +2079,17 @@ void hd_rad_team_user_kernel(RadArgs A) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int j = h + 4 * q;
-            const double kj = j < NN ? rl(oK + (j < NN ? j : 0), tt) : 0.0;
+            const double kj = j < NN ? rl(R::K + (j < NN ? j : 0), tt) : 0.0;
             const double at_ = bc<0>(cacc[q]), ab_ = bc<1>(cacc[q]);
             const double bt_ = bc<2>(cacc[q]), bb_ = bc<3>(cacc[q]);
             cpl[q] = 0.5 * (at_ + (kj > 0.0 ? -bt_ / kj : 0.0));
             cmi[q] = 0.5 * (ab_ - (kj > 0.0 ? -bb_ / kj : 0.0));
+            const int ce = (c ? RadCst<NN>::Cm : RadCst<NN>::Cp) + j;  // C- : C+
             if (ab0 == 0 && v < A.nu && j < NN && c < 2)
-              A.cst[((size_t)lc * 2 * NN + c * NN + j) * nu + v] = c ? cmi[q] : cpl[q];
+              A.cst[((size_t)lc * RadCst<NN>::size + ce) * nu + v] = c ? cmi[q] : cpl[q];
           }
         }
-        const double kc = c < NN ? rl(oK + (c < NN ? c : 0), tt) : 0.0;
+        const double kc = c < NN ? rl(R::K + (c < NN ? c : 0), tt) : 0.0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int r = h + 4 * q;
@@ -2117,7 +2107,7 @@ void hd_rad_team_user_kernel(RadArgs A) {
         const double mub = beam ? mu0 : 0.0;
         const double sx0 = sqrt(fmax(0.0, 1.0 - mub * mub));
         const double* lam = rad_lam<NN>(m);
-        double su = c_rtt.seed[m], s0v = su;
+        double su = c_rtt.co.seed[m], s0v = su;
         for (int k = 0; k < m; ++k) {
           su *= sxu;
           s0v *= sx0;
@@ -2131,7 +2121,7 @@ void hd_rad_team_user_kernel(RadArgs A) {
 #pragma unroll
           for (int p = 0; p < 2; ++p) {
             const int l = 2 * l2 + p;
-            const double cra = c_rtt.ra[m][l], crb = c_rtt.rb[m][l];
+            const double cra = c_rtt.co.ra[m][l], crb = c_rtt.co.rb[m][l];
             const double yu = l < m ? 0.0 : (l == m ? su : fma(cra * muu, y1u, -crb * y2u));
             const double y0 = l < m ? 0.0 : (l == m ? s0v : fma(cra * mub, y10, -crb * y20));
             y2u = y1u;
@@ -2178,8 +2168,8 @@ void hd_rad_team_user_kernel(RadArgs A) {
         const double ce = fam ? oth : own, cx = fam ? own : oth;
         const double cc = jok ? (fam ? cmi[q] : cpl[q]) : 0.0;
         const double am = cc * (fam ? ce - cx : ce + cx);  // hpl_j (c < 8), hmi_j (c >= 8)
-        const double kj = jok ? rl(oK + jj, tt) : 0.0;
-        const double ek = jok ? rl(oEk + jj, tt) : 1.0;
+        const double kj = jok ? rl(R::K + jj, tt) : 0.0;
+        const double ek = jok ? rl(R::Ek + jj, tt) : 1.0;
         // hpl's +k family decays along upward rays, hmi's along downward ones; the
         // other meets 1 - k|mu| -> 0
         const bool dec = (fam == 0) == up;
@@ -2189,8 +2179,8 @@ void hd_rad_team_user_kernel(RadArgs A) {
         amp[q] = am;
         kq[q] = kj;
         const double wi = jok ? Qc.w[jj] : 0.0;
-        const double zp = jok ? rl(oZp + jj, tt) : 0.0, zm = jok ? rl(oZm + jj, tt) : 0.0;
-        const double hr = jok ? rl(oH + jj, tt) : 0.0;
+        const double zp = jok ? rl(R::Zp + jj, tt) : 0.0, zm = jok ? rl(R::Zm + jj, tt) : 0.0;
+        const double hr = jok ? rl(R::H + jj, tt) : 0.0;
         sc = fma(wi * cu[q], fam ? zp - zm : zp + zm, sc);
         th = fma(wi, cu[q] * (fam ? hr : 1.0), th);
       }
@@ -2227,7 +2217,7 @@ void hd_rad_team_user_kernel(RadArgs A) {
         if (beam) {
           const double fac = (m == 0 ? 1.0 : 2.0) * fb / (4.0 * kPi);
           ab = fma(fac * x0, exp(-A.tauc[(size_t)lc * A.ns + sl] * rmu0), scs);
-          const double e0l = rl(oE0, tt);
+          const double e0l = rl(R::E0, tt);
           lay += upv ? ab * (1.0 - e0l * emv) / fma(av, rmu0, 1.0)
                      : ab * dexp(e0l, emv, fma(-av, rmu0, 1.0), lmv);
         }
@@ -2237,14 +2227,15 @@ void hd_rad_team_user_kernel(RadArgs A) {
           if (ssa == 1.0) ssa = 1.0 - kDither;
           const double f = ft[tt];
           const double om = ssa * (1.0 - f) / (1.0 - ssa * f);
-          const double bt = rl(oBt, tt), slope = rl(oSl, tt);
+          const double bt = rl(R::Bt, tt), slope = rl(R::Sl, tt);
           const double ce0 = (1.0 - om) + 2.0 * we;
           a1t = slope * ce0;
           a0 = fma(bt, ce0, 2.0 * slope * wo);
           lay += upv ? (a0 + a1t * mv) - (a0 + a1t * taup + a1t * mv) * emv
                      : (a0 + a1t * taup + a1t * mv) - (a0 + a1t * mv) * emv;
         }
-        if (iv < A.numu && v < A.nu) A.rsw[((size_t)lc * nu + v) * NE1 + iv] = lay;
+        if (iv < A.numu && v < A.nu)
+          RadUnitMajor::rec(A.rsw, NE1, lc, nu, v)[RadLay<NN>::Lay + iv] = lay;
         double* ap = aux + lane * 4;
         ap[0] = ab;
         ap[1] = a0;
@@ -2309,10 +2300,9 @@ void hd_rad_team_user_kernel(RadArgs A) {
 
 template <int NN>
 __global__ __launch_bounds__(256) void hd_rad_team_user_scan_kernel(RadArgs A) {
-  constexpr int nsym = NN * (NN + 1) / 2;
-  constexpr int NE1 = rad_layer_record_doubles(NN);
-  constexpr int NR = rad_rec_doubles(NN);
-  constexpr int oTp = nsym + NN * NN + 4 * NN + 2;
+  using R = RadRec<NN>;
+  constexpr int NE1 = RadOps<NN>::size;
+  constexpr int NR = R::size;
   const Quad<NN>& Qc = tquad<NN>(c_qt);
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t nu = A.nu;
@@ -2333,14 +2323,14 @@ __global__ __launch_bounds__(256) void hd_rad_team_user_scan_kernel(RadArgs A) {
   double cur = 0.0;
   if (m == 0) {
     if (up) {
-      const double* lv = A.lev + (size_t)L * 2 * NN * nu + u;
+      const double* lv = RadElemMajor::rec(A.lev, RadLev<NN>::size, L, nu, u);
       double fdn = 0.0;
-      for (int i = 0; i < NN; ++i) fdn = fma(Qc.g[i] * Qc.g[i], lv[(NN + i) * nu], fdn);
+      for (int i = 0; i < NN; ++i) fdn = fma(Qc.g[i] * Qc.g[i], lv[(RadLev<NN>::Im + i) * nu], fdn);
       fdn *= 2.0 * kPi;
       const double alb = A.albedo ? A.albedo[s] : 0.0;
       if (beam) {
         const double tb = A.tauc[(size_t)(L - 1) * A.ns + sl] +
-                          A.rrd[((size_t)(L - 1) * nu + u) * NR + oTp];
+                          RadUnitMajor::rec(A.rrd, NR, L - 1, nu, u)[R::Tp];
         fdn += fb * mu0 * exp(-tb * rmu0);
       }
       cur = alb / kPi * fdn + (A.planck ? (1.0 - alb) * A.planckv[(size_t)(L + 1) * A.ns + sl]
@@ -2356,9 +2346,9 @@ __global__ __launch_bounds__(256) void hd_rad_team_user_scan_kernel(RadArgs A) {
     const int lc = up ? L - 1 - step : step;
     const double ttop = A.taus[(size_t)lc * A.ns + sl];
     const double tbot = A.taus[(size_t)(lc + 1) * A.ns + sl];
-    const double taup = A.rrd[((size_t)lc * nu + u) * NR + oTp];
+    const double taup = RadUnitMajor::rec(A.rrd, NR, lc, nu, u)[R::Tp];
     const double emu = exp(-(taup / anu));
-    const double lay = A.rsw[((size_t)lc * nu + u) * NE1 + iu];
+    const double lay = RadUnitMajor::rec(A.rsw, NE1, lc, nu, u)[RadLay<NN>::Lay + iu];
     const double cin = cur;
     const double cout = fma(cin, emu, lay);
     const double tau = tbot - ttop;
@@ -2428,54 +2418,19 @@ hipError_t launch_rad_team_layer(int nn, const RadArgs& a, hipStream_t stream) {
       nn, [&](auto NN) { return launch_rad_layer<NN>(a, stream); });
 }
 
-template <int NN>
-static void fill_rad_team(RadTabTeam<NN>& t, const QuadHost& h) {
-  for (int m = 0; m < 2 * NN; ++m)
-    for (int i = 0; i < NN; ++i) {
-      const double x = h.mu[i];
-      double seed = 1.0;
-      for (int a = 1; a <= m; ++a) seed *= std::sqrt((2.0 * a - 1) / (2.0 * a));
-      seed *= std::pow(std::sqrt(std::fmax(0.0, 1.0 - x * x)), m);
-      double y1 = 0.0, y2 = 0.0;
-      for (int l = 0; l < 2 * NN; ++l) {
-        double v = 0.0;
-        if (l == m) v = seed;
-        else if (l > m)
-          v = ((2.0 * l - 1) * x * y1 - std::sqrt((double)(l - 1) * (l - 1) - (double)m * m) * y2) /
-              std::sqrt((double)l * l - (double)m * m);
-        t.lam[m][l][i] = v;
-        y2 = y1;
-        y1 = v;
-      }
-    }
-}
-
-// the Y_l^m tables of the team intensity kernels (hd_rad.hip's recurrence); called
-// once per device under hd_api.cpp's global table lock
+// the Y_l^m tables of the team intensity kernels; called once per device under
+// hd_api.cpp's global table lock
 hipError_t upload_rad_tables_team(const QuadHost* per_nn) {
   static RadTabsTeam c;  // ~570 KB: keep off the stack
-  fill_rad_team<9>(c.t9, per_nn[8]);
-  fill_rad_team<10>(c.t10, per_nn[9]);
-  fill_rad_team<11>(c.t11, per_nn[10]);
-  fill_rad_team<12>(c.t12, per_nn[11]);
-  fill_rad_team<13>(c.t13, per_nn[12]);
-  fill_rad_team<14>(c.t14, per_nn[13]);
-  fill_rad_team<15>(c.t15, per_nn[14]);
-  fill_rad_team<16>(c.t16, per_nn[15]);
-  for (int m = 0; m < 2 * kMaxNN; ++m) {
-    double sd = 1.0;
-    for (int a = 1; a <= m; ++a) sd *= std::sqrt((2.0 * a - 1) / (2.0 * a));
-    c.seed[m] = sd;
-    for (int l = 0; l < 2 * kMaxNN; ++l) {
-      if (l > m) {
-        const double den = std::sqrt((double)l * l - (double)m * m);
-        c.ra[m][l] = (2.0 * l - 1) / den;
-        c.rb[m][l] = std::sqrt((double)(l - 1) * (l - 1) - (double)m * m) / den;
-      } else {
-        c.ra[m][l] = c.rb[m][l] = 0.0;
-      }
-    }
-  }
+  fill_rad_tables(9, per_nn[8].mu, &c.t9.lam[0][0][0]);
+  fill_rad_tables(10, per_nn[9].mu, &c.t10.lam[0][0][0]);
+  fill_rad_tables(11, per_nn[10].mu, &c.t11.lam[0][0][0]);
+  fill_rad_tables(12, per_nn[11].mu, &c.t12.lam[0][0][0]);
+  fill_rad_tables(13, per_nn[12].mu, &c.t13.lam[0][0][0]);
+  fill_rad_tables(14, per_nn[13].mu, &c.t14.lam[0][0][0]);
+  fill_rad_tables(15, per_nn[14].mu, &c.t15.lam[0][0][0]);
+  fill_rad_tables(16, per_nn[15].mu, &c.t16.lam[0][0][0]);
+  fill_rad_coef(c.co);
   return hipMemcpyToSymbol(HIP_SYMBOL(c_rtt), &c, sizeof(RadTabsTeam), 0, hipMemcpyHostToDevice);
 }
 

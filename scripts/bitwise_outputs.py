@@ -170,6 +170,40 @@ def dump(out_dir):
         save("get_rad_" + tag, d.get_rad())
         save("radstatus_" + tag, st)
 
+    # ---- the rest of the intensity path's routes: nstr 16 with Planck and a beam (the
+    # user-angle maps' thermal vectors), fluxes at user depths only (nstr 8: the one-lane
+    # kernels; 24: team layer and sweep, rolled const and flux), nstr 2 (NN = 1), per-column
+    # rays at nstr 32 (the rolled user kernel)
+    nwave, ncol, nlyr = 2, 3, 6
+    umu6, phi3 = [-1.0, -0.6, -0.15, 0.1, 0.45, 0.8], [0.0, 75.0, 300.0]
+    rng = np.random.default_rng(8016)
+    prop, bc, temf = _inputs(rng, nwave, ncol, nlyr, 16, 1, 1)
+    prop[..., 0] = rng.uniform(0.3, 1.0, prop.shape[:3])
+    d = disort(16, nlyr, nwave, ncol, 1, flags="lamber,quiet,usrtau,usrang", user_tau=utau,
+               user_mu=umu6, user_phi=phi3)
+    save("radflux_n16_p1", d.forward(t(prop), tb(bc), t(temf)))
+    save("get_rad_n16_p1", d.get_rad())
+    for nstr in (8, 24):
+        rng = np.random.default_rng(8100 + nstr)
+        prop, bc, temf = _inputs(rng, nwave, ncol, nlyr, nstr, 1, 0)
+        prop[..., 0] = rng.uniform(0.3, 1.0, prop.shape[:3])
+        d = disort(nstr, nlyr, nwave, ncol, 1, flags="lamber,quiet,usrtau,onlyfl", user_tau=utau)
+        save(f"onlyfl_utau_n{nstr}_p1", d.forward(t(prop), tb(bc), t(temf)))
+    rng = np.random.default_rng(8002)
+    prop, bc, temf = _inputs(rng, nwave, ncol, nlyr, 2, 0, 1)
+    prop[..., 0] = rng.uniform(0.3, 1.0, prop.shape[:3])
+    d = disort(2, nlyr, nwave, ncol, 0, flags="lamber,quiet,usrtau,usrang", user_tau=utau,
+               user_mu=umu6, user_phi=phi3)
+    d.forward(t(prop), tb(bc))
+    save("get_rad_n2", d.get_rad())
+    rng = np.random.default_rng(8032)
+    prop, bc, temf = _inputs(rng, nwave, ncol, nlyr, 32, 0, 1)
+    prop[..., 0] = rng.uniform(0.3, 1.0, prop.shape[:3])
+    umu = rng.uniform(0.1, 1.0, (ncol, 7)) * rng.choice([-1.0, 1.0], (ncol, 7))
+    phi = rng.uniform(0.0, 360.0, (ncol, 7))
+    d = disort(32, nlyr, nwave, ncol, 0, flags="lamber,quiet,usrtau", user_tau=utau)
+    save("rays_percol_n32", d.forward_rays(t(prop), tb(bc), umu=t(umu), phi=t(phi)))
+
     # ---- Beer-Lambert
     rng = np.random.default_rng(555)
     nstr, nlyr, nwave, ncol = 8, 17, 5, 11

@@ -108,8 +108,8 @@ def _random_case(rng, nwave, ncol, nlyr, nstr, planck, rayleigh=False):
 @pytest.mark.parametrize("nstr", [2, 4, 6, 8, 12, 16, 18, 24, 32])
 @pytest.mark.parametrize("planck", [False, True])
 def test_radiances_vs_oracle(nstr, planck):
-    """Every azimuthal mode, user depths and angles; nstr 18..32 run the same
-    kernels compiled with rolled loops (hd_rad_wide.hip)."""
+    """Every azimuthal mode, user depths and angles; nstr 18..32 run the team kernels
+    (hd_team_mfma.hip) and the rolled flux kernel (hd_rad_wide.hip)."""
     rng = np.random.default_rng(500 + nstr + 50 * planck)
     nwave, ncol, nlyr = 2, 3, 6
     prop, bc, kw = _random_case(rng, nwave, ncol, nlyr, nstr, planck)
@@ -189,14 +189,23 @@ def test_level_fluxes_match_flux_path(nstr):
     assert rel_err(fa, fb).max() < 1e-9
 
 
-def test_onlyfl_user_depths_vs_oracle():
+@pytest.mark.parametrize("nstr", [8, 18, 32])
+@pytest.mark.parametrize("planck", [False, True])
+def test_onlyfl_user_depths_vs_oracle(nstr, planck):
+    """usrtau,onlyfl: the fluxes at nine user depths, no user angles.  nstr 8: the one-lane
+    layer, sweep, const and flux kernels; nstr 18 and 32: team layer -> team sweep -> the
+    rolled const and flux kernels (hd_rad_wide.hip)."""
     rng = np.random.default_rng(12)
-    prop, bc, kw = _random_case(rng, 2, 2, 7, 8, False)
+    prop, bc, kw = _random_case(rng, 2, 2, 7, nstr, planck)
     total = prop[..., 0].sum(axis=-1).min()
     utau = np.linspace(0, total, 9)
-    d = _disort(8, 7, 2, 2, flags="usrtau,onlyfl,lamber", utau=utau)
-    flux = d.forward(torch.as_tensor(prop, device=DEV), _dev(bc)).cpu().numpy()
-    fref, _ = disort_rad_forward(prop, bc, nstr=8, umu=[0.5], phi=[0.0], utau=utau, onlyfl=True)
+    d = _disort(nstr, 7, 2, 2, flags="usrtau,onlyfl,lamber", utau=utau, planck=planck,
+                wl=kw.get("wave_lower"), wu=kw.get("wave_upper"))
+    t = None if "temf" not in kw else torch.as_tensor(kw["temf"], device=DEV)
+    flux = d.forward(torch.as_tensor(prop, device=DEV), _dev(bc), t).cpu().numpy()
+    fref, _ = disort_rad_forward(prop, bc, kw.get("temf"), nstr=nstr, umu=[0.5], phi=[0.0],
+                                 utau=utau, onlyfl=True, planck=planck,
+                                 wave_lower=kw.get("wave_lower"), wave_upper=kw.get("wave_upper"))
     assert flux.shape == (2, 2, 9, 2)
     assert margin(rel_err(flux, fref).max()) < TOL
     with pytest.raises(RuntimeError):
