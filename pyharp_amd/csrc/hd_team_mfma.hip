@@ -15,12 +15,20 @@
 //     hd_team_mfma_layer_spher_kernel<NN, NT>  FluxLayerPath<NT, true>: pseudo-spherical beam
 //     hd_rad_team_layer_kernel<NN>             RadLayerPath: problem = (solve, azimuthal
 //                                              mode), the radiance records kept
-//   hd_team_mfma_sweep_*_kernel    one wave = four solves: adding sweep top->bottom,
+//   team_sweep_body<NN, Path>      one wave = four problems: adding sweep top->bottom,
 //                                  Lambertian surface, back-substitution, level
-//                                  fluxes in harp layout  [c_setmtx, c_solve0,
-//                                  c_fluxes]
+//                                  fluxes in harp layout or level intensities
+//                                  [c_setmtx, c_solve0, c_fluxes].  Stated once;
+//                                  its four kernels declare the LDS and name a path:
+//     hd_team_mfma_sweep_lean_kernel<NN, NT>     LeanSweepPath<NT>: hd_solve / hd_solve_band,
+//                                                two waves per SIMD
+//     hd_team_mfma_sweep_flx_kernel<NN>          FluxSweepPath<true, false>: hd_solve_flx
+//     hd_team_mfma_sweep_spher_kernel<NN, FLX>   FluxSweepPath<FLX, true>: pseudo-spherical beam
+//     hd_rad_team_sweep_kernel<NN>               RadSweepPath: problem = (solve, azimuthal
+//                                                mode), the stack state kept per level
 //
-// Scratch records, solve-major inside a layer (a team's record is contiguous):
+// Scratch records of the flux paths, solve-major inside a layer (a team's record is
+// contiguous; FluxOpsRec, FluxBsubRec; the intensity path's: hd_rad_layout.hpp):
 //   layer ops [lc][s][2NN^2+2NN+2]  R~ rows | T~ rows | S~+ | S~- | tau' | pad
 //   back-sub  [lc][s][NN^2+2NN+1 -> even]  ZT rows | t | rc | cs | pad
 //
@@ -332,6 +340,198 @@ __device__ __forceinline__ void phase_rows_mode(const double* q, int nm, double 
     });
   }
 }
+
+// ---- the pieces of team_sweep_body's layer step (lane i of a team holds row i) ----
+// LU of W1's rows without pivoting; reciprocal pivots on the diagonal.  PIN: a
+// step's broadcasts stay in that step (the two-waves-per-SIMD path)
+template <int NN, bool PIN>
+__device__ __forceinline__ void team_lu(double (&w)[NN], int i, int& st) {
+  sfor<0, NN>([&](auto K) {
+    constexpr int k = HD_K(K);
+    const double piv = bc<k>(w[k]);
+    if (!(fabs(piv) > 1.0e-12)) st |= kStPivot;
+    const double rp = rcp_nr(piv);
+    const double lik = w[k] * rp;
+    const double mm = i > k ? lik : 0.0;
+    w[k] = i == k ? rp : (i > k ? lik : w[k]);
+    sfor<k + 1, NN>([&](auto J) {
+      constexpr int j = HD_K(J);
+      w[j] = fma(-mm, bc<k>(w[j]), w[j]);
+    });
+    if constexpr (PIN) pin<NN>(w);
+  });
+}
+// x <- W1^-1 x from team_lu's rows: forward with the unit lower factor, then backward
+template <int NN>
+__device__ __forceinline__ void team_lu_solve(const double (&w)[NN], int i, double& x) {
+  sfor<0, NN>([&](auto K) {
+    constexpr int k = HD_K(K);
+    const double tk = bc<k>(x);
+    if (i > k) x = fma(-w[k], tk, x);
+  });
+  sfor_rev<0, NN>([&](auto K) {
+    constexpr int k = HD_K(K);
+    if (i == k) x *= w[k];
+    const double tk = bc<k>(x);
+    if (i < k) x = fma(-w[k], tk, x);
+  });
+}
+// The columns of L^-1 (unit lower) and U^-1 from team_lu's rows -- lane i holds column
+// i, i.e. row i of the transposed inverse, the operand the M-layout product wants.
+// ZT = W1^-1 T = U^-1 (L^-1 T) then runs on the matrix core instead of sixteen
+// row-sequential triangular solves with T's sixteen columns (NN(NN-1) broadcasts per
+// lane against 2 x NN(NN-1)/2 here)
+template <int NN>
+__device__ __forceinline__ void team_lu_inverse_cols(double (&w)[NN], int i, double msk,
+                                                     double (&zl)[NN], double (&zu)[NN]) {
+  sfor<0, NN>([&](auto R) {  // column i of L^-1: z_r = delta_ri - sum_{k<r} L_rk z_k
+    constexpr int r = HD_K(R);
+    double v = i == r ? 1.0 : 0.0;
+    sfor<0, r>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zl[HD_K(K)], v); });
+    zl[r] = v;
+    pin<NN>(w);
+  });
+  sfor_rev<0, NN>([&](auto R) {  // column i of U^-1: z_r = (delta_ri - sum_{k>r} U_rk z_k) / U_rr
+    constexpr int r = HD_K(R);
+    double v = i == r ? 1.0 : 0.0;
+    sfor<r + 1, NN>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zu[HD_K(K)], v); });
+    zu[r] = v * bc<r>(w[r]);  // reciprocal pivot on the diagonal
+    pin<NN>(w);
+  });
+  sfor<0, NN>([&](auto J) {
+    zl[HD_K(J)] *= msk;
+    zu[HD_K(J)] *= msk;
+  });
+}
+// Lambertian surface under the whole stack (reflection rows ra, downward source sd,
+// emission esurf(), evaluated after the team sums): the amplitude x of I+ = g x, and
+// rgrow = (A g)_i
+template <int NN, class E>
+__device__ __forceinline__ double team_lambert(const double (&ra)[NN], const Quad<NN>& Qc,
+                                               double g_i, double sd, double alb, E&& esurf,
+                                               double& rgrow) {
+  rgrow = 0.0;
+  sfor<0, NN>([&](auto J) { rgrow = fma(ra[HD_K(J)], Qc.g[HD_K(J)], rgrow); });
+  const double gsd = bc<0>(team_sum(g_i * sd));
+  const double grg = bc<0>(team_sum(g_i * rgrow));
+  return (2.0 * alb * gsd + esurf()) / (1.0 - 2.0 * alb * grg);
+}
+
+// ---- the paths of team_sweep_body ------------------------------------------------
+// A path names its kernel's argument struct, what a problem is and where its records
+// lie, and switches the parts of the body that are not common.
+// Problem: a solve (sl, s = solve_of(...), A.nsc of them), or with kModes a unit
+// u = m * ns + sl of azimuthal mode m (A.nu of them, per-solve arrays of stride A.ns;
+// Lambert surface, isotropic top and direct beam at m = 0 only).
+// Records: Ops<NN> is the layer-operator record read from ops(A) and Bsub<NN> the
+// back-substitution record written to A.bsub, both [layer][problem][element]; Ops'
+// elem(r, c) is where entry (r, c) of R~ (from Ops::R) and T~ (from Ops::T) lies --
+// full rows on a flux path, packed upper (RadOps, sym_index) with kModes; rec() is how the
+// body holds a problem's record (LaneRec or LayerRec, below).
+// The downward pass records per level rc and cs (kFlx: also rh_i = sum_j A(i,j) h_j and
+// ch = h . Sd, h = g / mu, for the mean intensities), or with kModes the stack state
+// R_above (packed upper) and S_down; t1 and ZT go to Bsub's Tv and Z on every path.
+// The upward pass emits the two fluxes of every level, kFlx the eight components of
+// hd_solve_flx (F->flx), kModes I+- / g to lev.  kSpher: the direct beam at a level
+// from hd_spher_kernel's ch' (P->chp) in place of exp(-tau_c / mu0).
+// kSink: the ZT stores are branch-free, an element the lane does not own going to
+// A.sink + lane (else plain predicated stores); kNT: they are nontemporal.
+// kLaneSink is the same question for the team vectors (t1, rc, rh, S_down), and a flag
+// of its own because LeanSweepPath answers the two differently: its ZT stores are
+// branch-free, its vectors go, as on the flux paths, to a record at A.sink.
+// kResident: R~, T~ (M layout and team rows) and S~+- are loaded at the top of the
+// layer step and A's team rows stay in registers -- one wave per SIMD: at two (256
+// registers) that form spills 144 VGPRs and ran C5 at 0.81M solves/s against 1.02M
+// (DESIGN.md section 9).  LeanSweepPath is the form that does fit two waves (and one
+// beside a 240-register layer-kernel wave); only where the operands live between
+// their uses changes, the arithmetic and its order do not:
+//   * A's team rows (for the level's rc, and u = A t1 + Sd) stay in LDS tile set S0
+//     from the end of one layer to the middle of the next; W1 = I - R A goes through
+//     tile set S1 instead;
+//   * R~ and T~ are read from the layer record where they are needed -- R~ (M layout)
+//     for W1 and again for A <- R~ + T~ (A ZT), R~'s team row for t1, T~'s team row
+//     for Sd, T~ (M layout) for the ZT products (second reads are L2 hits);
+//   * per-element record offsets are recomputed where they are used (laundered lane
+//     indices), not hoisted out of the layer loop.
+// tests/test_gpu_flx.py::test_team_flup_bitwise_with_hd_solve holds the two forms equal.
+
+// Problem v's record in layer lc of a [layer][problem][element] buffer, two ways to hold
+// it.  LaneRec: one pointer per lane and layer (the flux kernels' form).  LayerRec: the
+// layer's uniform base and the lane's offset v * size, added at each access -- the
+// radiance sweep's form: with a pointer per lane it needs 8 - 32 more registers at every
+// NN and spills at NN 15 (profiles/teamsweep/README.md; with this form
+// hd_rad_team_sweep_kernel<15> sits at 250 of the 256 AGPRs, no spill)
+template <class T>
+struct LaneRec {
+  T* p;
+  __device__ __forceinline__ T& operator[](int e) const { return p[e]; }
+  __device__ __forceinline__ T* operator+(int e) const { return p + e; }
+};
+template <class T>
+struct LayerRec {
+  T* base;
+  size_t off;
+  __device__ __forceinline__ T& operator[](int e) const { return base[off + e]; }
+  __device__ __forceinline__ T* operator+(int e) const { return base + (off + e); }
+};
+template <int NN>
+struct FluxOpsRec {  // layer ops: R~ rows | T~ rows | S~+ | S~- | tau' | pad
+  static constexpr int R = 0, T = NN * NN, Sp = 2 * NN * NN, Sm = Sp + NN, Tau = Sm + NN;
+  static constexpr int size = ne1t<NN>();
+  static __device__ __forceinline__ int elem(int r, int c) { return r * NN + c; }
+};
+template <int NN, bool FLX>
+struct FluxBsubRec {  // back-sub: ZT rows | t | rc | cs | (FLX: rh | ch) | pad
+  static constexpr int Z = 0, Tv = NN * NN, Rc = Tv + NN, Cs = Rc + NN, Rh = Cs + 1, Ch = Rh + NN;
+  static constexpr int size = FLX ? ne2tf<NN>() : ne2t<NN>();
+};
+template <int NN>
+struct RadOpsRec : RadOps<NN> {
+  static __device__ __forceinline__ int elem(int r, int c) { return sym_index<NN>(r, c); }
+};
+template <bool FLX>
+struct SolveSweepPath {  // problem = solve: what the flux and lean paths share
+  using Args = SweepArgs;
+  template <int NN> using Ops = FluxOpsRec<NN>;
+  template <int NN> using Bsub = FluxBsubRec<NN, FLX>;
+  static constexpr bool kModes = false, kFlx = FLX;
+  static __device__ __forceinline__ int problems(const Args& A) { return A.nsc; }
+  static __device__ __forceinline__ int solves(const Args& A) { return A.nsc; }
+  static __device__ __forceinline__ long solve(const Args& A, int sl) {
+    return solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
+  }
+  static __device__ __forceinline__ const double* ops(const Args& A) { return A.scr; }
+  template <class T>
+  static __device__ __forceinline__ LaneRec<T> rec(T* buf, int size, int lc, size_t np, int v) {
+    return {buf + ((size_t)lc * np + v) * size};
+  }
+};
+template <bool FLX, bool SPHER>
+struct FluxSweepPath : SolveSweepPath<FLX> {
+  static constexpr bool kSpher = SPHER, kResident = true, kSink = false, kNT = false;
+  static constexpr bool kLaneSink = false;
+};
+template <bool NT>
+struct LeanSweepPath : SolveSweepPath<false> {
+  static constexpr bool kSpher = false, kResident = false, kSink = true, kNT = NT;
+  static constexpr bool kLaneSink = false;
+};
+struct RadSweepPath {
+  using Args = RadArgs;
+  template <int NN> using Ops = RadOpsRec<NN>;
+  template <int NN> using Bsub = RadBsub<NN>;
+  static constexpr bool kModes = true, kFlx = false;
+  static constexpr bool kSpher = false, kResident = true, kSink = true, kNT = false;
+  static constexpr bool kLaneSink = true;
+  static __device__ __forceinline__ int problems(const Args& A) { return A.nu; }
+  static __device__ __forceinline__ int solves(const Args& A) { return A.ns; }
+  static __device__ __forceinline__ long solve(const Args& A, int sl) { return A.s0 + sl; }
+  static __device__ __forceinline__ const double* ops(const Args& A) { return A.rsw; }
+  template <class T>
+  static __device__ __forceinline__ LayerRec<T> rec(T* buf, int size, int lc, size_t np, int v) {
+    return {buf + (size_t)lc * size * np, (size_t)v * size};
+  }
+};
 
 }  // namespace
 
@@ -848,31 +1048,28 @@ __global__ __launch_bounds__(64, 2) void hd_team_mfma_layer_spher_kernel(LayerAr
 }
 
 // ============================================================================
-// K2 (team, MFMA): adding sweep + back-substitution, four solves per wave.
+// K2 (team, MFMA): adding sweep + back-substitution, four problems per wave -- the
+// one body behind hd_team_mfma_sweep_flx_kernel, hd_team_mfma_sweep_spher_kernel
+// (FluxSweepPath), hd_team_mfma_sweep_lean_kernel (LeanSweepPath) and
+// hd_rad_team_sweep_kernel (RadSweepPath).
 // The register/team sweep's update per layer
 //   W1 = I - R A,  ZT = W1^-1 T,  A <- R + T A ZT,  Sd <- T (A t1 + Sd) + S-
 // (A = reflection of the stack above, t1 = W1^-1 (R Sd + S+)) with the three
 // dense 16 x 16 products (R A, A ZT, T (A ZT)) on the matrix core in the M
 // layout -- R~, T~ and A are symmetric, so each is its own transpose operand --
 // and the pivot-free LU of W1, the ZT solves and the vectors on the VALU in the
-// team layout (lane i = row i); W1 goes M -> T and ZT
-// T -> M through LDS, A is kept in both layouts.  The back-substitution pass reads
-// its records in the team layout.  One wave per SIMD: at
-// two (256 registers) it spills 144 VGPRs and ran C5 at 0.81M solves/s against
-// 1.02M here and 0.97M for a VALU-product sweep.
-// hd_solve's sweep is the lean kernel below; this body runs as the flx and spher sweeps.
-// FLX (hd_solve_flx, always built): the back-substitution record is widened by the
-// mean-intensity row rh_i = sum_j A(i,j) h_j and the scalar ch = h . Sd, h = g / mu,
-// after cs (stride ne2tf), and the upward pass emits the eight components of every
-// level to F->flx instead of the two fluxes.
+// team layout (lane i = row i); W1 goes M -> T and ZT T -> M through LDS, A is kept
+// in both layouts.  Then the Lambertian surface and the back-substitution pass
+// I+ <- t1 + ZT I+ bottom -> top, which reads its records in the team layout.
 // ============================================================================
-// SPHER (pseudo-spherical beam): the direct beam at every level from hd_spher_kernel's ch'.
-template <int NN, bool FLX, bool SPHER = false>
-__device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const FlxArgs* F,
-                                                     double* lds, const SphArgs* P = nullptr) {
-  constexpr int ne2 = FLX ? ne2tf<NN>() : ne2t<NN>();
+template <int NN, class Path>
+__device__ __forceinline__ void team_sweep_body(const typename Path::Args& A, const FlxArgs* F,
+                                                const SphArgs* P, double* lds) {
+  using O = typename Path::template Ops<NN>;
+  using B = typename Path::template Bsub<NN>;
   double* S0 = lds;
   double* S1 = lds + kSet;
+  double* SW = Path::kResident ? S0 : S1;  // W1's tile set
   const Quad<NN>& Qc = tquad<NN>(c_qt);
   const int lane = (int)threadIdx.x;
   const int h = lane >> 4, c = lane & 15;  // M layout
@@ -880,259 +1077,320 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
   const bool act = i < NN;
   const int ii = act ? i : 0;
   const int grp = (int)blockIdx.x;
+  const int npb = Path::problems(A);  // problems in this chunk (= record stride)
+  const int ns = Path::solves(A);     // solves in this chunk (= stride of planckv and chp)
   // every lane takes part in the MFMA / LDS / DPP exchanges: a team past the end
-  // repeats the block's first solve and stores nothing
-  const bool valid = grp * 4 + t < A.nsc;
-  const int sl = valid ? grp * 4 + t : grp * 4;
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
+  // repeats the block's first problem and stores nothing
+  const bool valid = grp * 4 + t < npb;
+  const int u = valid ? grp * 4 + t : grp * 4;
+  const int m = Path::kModes ? u / ns : 0;
+  const int sl = u - m * ns;
+  const long s = Path::solve(A, sl);
   const int L = A.nlyr;
-  const size_t nsc = A.nsc;
+  const size_t np = npb;
   int st = 0;
   const double msk = act ? 1.0 : 0.0;
   const double g_i = Qc.g[ii] * msk;
-  const double h_i = g_i * Qc.rmu[ii];
+  const double h_i = g_i * Qc.rmu[ii];  // kFlx
+  const double rg_i = Qc.rg[ii] * msk;  // kModes
+  const bool wr = valid && act;
+  int um[4];  // team tt's problem, for the loads and stores of the M layout
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) um[tt] = grp * 4 + tt < npb ? grp * 4 + tt : grp * 4;
 
-  for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;
+  for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;  // A = 0 in S0
   lds_fence();
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
   bool beam = fb > 0.0 && mu0 > 0.0;
-  if constexpr (SPHER) beam = beam && P->chp[(size_t)(L + 1) * nsc + sl] != 0.0;
-  const double alb = A.albedo ? A.albedo[s] : 0.0;
+  if constexpr (Path::kSpher) beam = beam && P->chp[(size_t)(L + 1) * ns + sl] != 0.0;
+  double alb = A.albedo ? A.albedo[s] : 0.0;
   if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
   double top = A.fisot ? A.fisot[s] : 0.0;
   double bsurf = 0.0;
   if (A.planck) {
-    bsurf = A.planckv[(size_t)(L + 1) * nsc + sl];
-    top += A.planckv[(size_t)(L + 2) * nsc + sl];
+    bsurf = A.planckv[(size_t)(L + 1) * ns + sl];
+    top += A.planckv[(size_t)(L + 2) * ns + sl];
   }
+  if (m > 0) alb = top = bsurf = 0.0;  // Lambert surface, isotropic top: mode 0 only
   const double twopi = 2.0 * kPi;
   const double rmu0 = beam ? 1.0 / mu0 : 0.0;
-  const double f0mu0 = beam ? fb * mu0 : 0.0;
-  // direct beam at solver level lc (1 without a beam)
+  const double f0mu0 = (beam && m == 0) ? fb * mu0 : 0.0;
+  // direct beam at solver level lc (kSpher: 1 without a beam)
   auto beam_at = [&](int lc, double tauc) {
-    if constexpr (SPHER) return beam ? exp(-P->chp[(size_t)lc * nsc + sl]) : 1.0;
+    if constexpr (Path::kSpher) return beam ? exp(-P->chp[(size_t)lc * ns + sl]) : 1.0;
     else return exp(-tauc * rmu0);
   };
 
-  // the wave's four solves in M layout: problem tt's records
-  int slm[4];
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) slm[tt] = grp * 4 + tt < A.nsc ? grp * 4 + tt : grp * 4;
-
   double ram[4][4];  // A (M layout)
-  double ra[NN];     // A row i (T layout)
+  double ra[NN];     // A row i (T layout): kResident keeps it, else read from S0 where used
   double sd = g_i * top;
 #pragma unroll
   for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-    for (int m = 0; m < 4; ++m) ram[tt][m] = 0.0;
+    for (int q = 0; q < 4; ++q) ram[tt][q] = 0.0;
   sfor<0, NN>([&](auto J) { ra[HD_K(J)] = 0.0; });
   double tauc = 0.0;
 
   for (int lc = 0; lc < L; ++lc) {
-    const double* rec = A.scr + ((size_t)lc * nsc + sl) * ne1t<NN>();
-    double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2;
-    double* bw = (act && valid) ? bp : A.sink;
-    // R~, T~ of the four problems in M layout (zero padding beyond NN)
-    double rm[4][4], tm[4][4];
+    // !kResident: the lane indices, laundered per layer: every lane-dependent constant
+    // below (identity entries, triangle masks) is then formed where it is used instead
+    // of all being hoisted out of the loop into live (and spilled) registers
+    int i_ = i, h_ = h, c_ = c;
+    if constexpr (!Path::kResident) asm volatile("" : "+v"(i_), "+v"(h_), "+v"(c_));
+    const int i = i_, h = h_, c = c_;
+    const auto rec = Path::rec(Path::ops(A), O::size, lc, np, u);
+    const auto bp = Path::rec(A.bsub, B::size, lc, np, u);
+    // lane i's element of a team vector at e of the bsub record.  kLaneSink: a lane that
+    // owns none stores to A.sink + lane (RadArgs::sink holds 64 doubles), else to the
+    // same element of a record at A.sink (SweepArgs::sink holds one)
+    double* bw = nullptr;
+    if constexpr (!Path::kLaneSink) bw = wr ? bp + 0 : A.sink;
+    auto vec_dst = [&](int e) {
+      if constexpr (Path::kLaneSink) return wr ? bp + (e + i) : A.sink + lane;
+      else return bw + (e + ii);
+    };
+    // R~ (off = O::R) or T~ (O::T) of the four problems in M layout, zero beyond NN, and
+    // this problem's row of it in T layout.  !kResident: issued where they stand, not
+    // hoisted into an earlier phase, with laundered indices (above)
+    auto load_m = [&](int off, double (&x)[4][4]) {
+      if constexpr (!Path::kResident) __builtin_amdgcn_sched_barrier(0);
+      int hl = h, cl = c;
+      if constexpr (!Path::kResident) asm volatile("" : "+v"(hl), "+v"(cl));
 #pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const double* rt = A.scr + ((size_t)lc * nsc + slm[tt]) * ne1t<NN>();
+      for (int tt = 0; tt < 4; ++tt) {
+        const double* rt = Path::rec(Path::ops(A), O::size, lc, np, um[tt]) + off;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int r = h + 4 * m;
-        const bool in = r < NN && c < NN;
-        const int e = in ? r * NN + c : 0;
-        rm[tt][m] = in ? rt[e] : 0.0;
-        tm[tt][m] = in ? rt[NN * NN + e] : 0.0;
+        for (int q = 0; q < 4; ++q) {
+          const int r = hl + 4 * q;
+          const bool in = r < NN && cl < NN;
+          x[tt][q] = in ? rt[in ? O::elem(r, cl) : 0] : 0.0;
+        }
       }
+    };
+    auto load_row = [&](int off, double (&x)[NN]) {
+      if constexpr (!Path::kResident) __builtin_amdgcn_sched_barrier(0);
+      int il = ii;
+      if constexpr (!Path::kResident) asm volatile("" : "+v"(il));
+      sfor<0, NN>([&](auto J) { x[HD_K(J)] = rec[off + O::elem(il, HD_K(J))] * msk; });
+    };
+    // A's row i where it is used
+    auto a_row = [&] {
+      if constexpr (!Path::kResident) {
+        get_rows<NN>(S0, t, i, ra);
+        sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
+      }
+    };
+    // kResident: the layer's operands, all at the top of the step
+    double rm[4][4], tm[4][4], rl[NN], tr[NN];
+    if constexpr (Path::kResident) {
+      load_m(O::R, rm);
+      load_m(O::T, tm);
+      load_row(O::R, rl);
+      load_row(O::T, tr);
     }
-    // this problem's rows in T layout
-    double rl[NN], tr[NN];
-    sfor<0, NN>([&](auto J) {
-      rl[HD_K(J)] = rec[ii * NN + HD_K(J)] * msk;
-      tr[HD_K(J)] = rec[NN * NN + ii * NN + HD_K(J)] * msk;
-    });
     // direct beam at the layer top; a unit-beam record's sources scale with it
-    const double eb = beam_at(lc, tauc);
-    const double sscale = A.beam_scale ? eb : 1.0;
-    const double spl = rec[2 * NN * NN + ii] * msk * sscale;
-    const double sml = rec[2 * NN * NN + NN + ii] * msk * sscale;
+    double eb = 1.0, sscale = 1.0;
+    if constexpr (!Path::kModes) {
+      eb = beam_at(lc, tauc);
+      sscale = A.beam_scale ? eb : 1.0;
+    }
+    const double spl = rec[O::Sp + ii] * msk * sscale;
+    double sml = 0.0;
+    if constexpr (Path::kResident) sml = rec[O::Sm + ii] * msk * sscale;
 
-    // level lc (top of layer lc): F_dn = rc . I+ + cs
-    {
+    // ---- what the downward pass records at level lc (top of layer lc) ----
+    a_row();
+    if constexpr (Path::kModes) {
+      // the stack above this layer: R_above (packed upper, row i from j = i) and S_down.
+      // Branch-free: the elements a lane does not own go to the sink
+      double* urow = bp + (B::Ra + sym_index<NN>(ii, ii) - ii);
+      sfor<0, NN>([&](auto J) {
+        constexpr int j = HD_K(J);
+        double* dst = (wr && j >= i) ? urow + j : A.sink + lane;
+        *dst = ra[j];
+      });
+      *vec_dst(B::Sd) = sd;
+    } else {  // F_dn = rc . I+ + cs
       double tq = 0.0;
       sfor<0, NN>([&](auto J) { tq = fma(ra[HD_K(J)], Qc.g[HD_K(J)], tq); });
-      bw[NN * NN + NN + ii] = twopi * tq;
+      *vec_dst(B::Rc) = twopi * tq;
       const double cs = team_sum(g_i * sd);
-      if (i == 0 && valid) bp[NN * NN + 2 * NN] = fma(twopi, cs, f0mu0 * eb);
-      if constexpr (FLX) {
+      if (i == 0 && valid) bp[B::Cs] = fma(twopi, cs, f0mu0 * eb);
+      if constexpr (Path::kFlx) {
         double th = 0.0;
         sfor<0, NN>([&](auto J) {
           th = fma(ra[HD_K(J)], Qc.g[HD_K(J)] * Qc.rmu[HD_K(J)], th);
         });
-        bw[NN * NN + 2 * NN + 1 + ii] = th;
+        *vec_dst(B::Rh) = th;
         const double ch = team_sum(h_i * sd);
-        if (i == 0 && valid) bp[NN * NN + 3 * NN + 1] = ch;
+        if (i == 0 && valid) bp[B::Ch] = ch;
       }
     }
+    // ---- the layer step ----
     // W1 = I - R A on the matrix core, to team rows through LDS
     {
       double pw[4][4];
+      if constexpr (!Path::kResident) load_m(O::R, rm);
       mprod<false>(rm, ram, pw, h, c);
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) pw[tt][m] = (h + 4 * m == c ? 1.0 : 0.0) - pw[tt][m];
+        for (int q = 0; q < 4; ++q) pw[tt][q] = (h + 4 * q == c ? 1.0 : 0.0) - pw[tt][q];
       lds_fence();
-      put_m(S0, h, c, pw);
+      put_m(SW, h, c, pw);
       lds_fence();
     }
     double w[NN];
-    get_rows<NN>(S0, t, i, w);
+    get_rows<NN>(SW, t, i, w);
     sfor<0, NN>([&](auto J) { w[HD_K(J)] *= msk; });
-    // t1 = R Sd + S+
+    // t1 = W1^-1 (R Sd + S+)
     double t1 = spl;
+    if constexpr (!Path::kResident) load_row(O::R, rl);
     sfor<0, NN>([&](auto K) { t1 = fma(rl[HD_K(K)], bc<HD_K(K)>(sd), t1); });
-    // LU without pivoting; reciprocal pivots on the diagonal
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double piv = bc<k>(w[k]);
-      if (!(fabs(piv) > 1.0e-12)) st |= kStPivot;
-      const double rp = rcp_nr(piv);
-      const double lik = w[k] * rp;
-      const double mm = i > k ? lik : 0.0;
-      w[k] = i == k ? rp : (i > k ? lik : w[k]);
-      sfor<k + 1, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        w[j] = fma(-mm, bc<k>(w[j]), w[j]);
-      });
-    });
-    // t1 <- W1^-1 t1
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double tk = bc<k>(t1);
-      if (i > k) t1 = fma(-w[k], tk, t1);
-    });
-    sfor_rev<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      if (i == k) t1 *= w[k];
-      const double tk = bc<k>(t1);
-      if (i < k) t1 = fma(-w[k], tk, t1);
-    });
+    team_lu<NN, !Path::kResident>(w, i, st);
+    team_lu_solve<NN>(w, i, t1);
     // u = A t1 + Sd
-    double u = sd;
-    sfor<0, NN>([&](auto K) { u = fma(ra[HD_K(K)], bc<HD_K(K)>(t1), u); });
-    bw[NN * NN + ii] = t1;
-    // ZT = W1^-1 T = U^-1 (L^-1 T) on the matrix core: the team forms the columns
-    // of L^-1 (unit lower) and U^-1 from the LU rows -- lane i holds column i, i.e.
-    // row i of the transposed inverse, the operand the M-layout product wants --
-    // instead of sixteen row-sequential triangular solves with T's sixteen columns
-    // (NN(NN-1) broadcasts per lane against 2 x NN(NN-1)/2 here)
+    double uv = sd;
+    a_row();
+    sfor<0, NN>([&](auto K) { uv = fma(ra[HD_K(K)], bc<HD_K(K)>(t1), uv); });
+    *vec_dst(B::Tv) = t1;
     {
       double zl[NN], zu[NN];
-      sfor<0, NN>([&](auto R) {  // column i of L^-1: z_r = delta_ri - sum_{k<r} L_rk z_k
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<0, r>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zl[HD_K(K)], v); });
-        zl[r] = v;
-        pin<NN>(w);
-      });
-      sfor_rev<0, NN>([&](auto R) {  // column i of U^-1: z_r = (delta_ri - sum_{k>r} U_rk z_k) / U_rr
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<r + 1, NN>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zu[HD_K(K)], v); });
-        zu[r] = v * bc<r>(w[r]);  // reciprocal pivot on the diagonal
-        pin<NN>(w);
-      });
-      sfor<0, NN>([&](auto J) {
-        zl[HD_K(J)] *= msk;
-        zu[HD_K(J)] *= msk;
-      });
+      team_lu_inverse_cols<NN>(w, i, msk, zl, zu);
       lds_fence();
-      put_rows<NN>(S0, t, i, zl);  // L^-T, row-major
+      put_rows<NN>(S0, t, i, zl);  // L^-T, row-major (A's rows in S0 are done)
       put_rows<NN>(S1, t, i, zu);  // U^-T, row-major
     }
     // Sd <- T u + S-
     {
+      if constexpr (!Path::kResident) {
+        load_row(O::T, tr);
+        sml = rec[O::Sm + ii] * msk * sscale;
+      }
       double tq = sml;
-      sfor<0, NN>([&](auto K) { tq = fma(tr[HD_K(K)], bc<HD_K(K)>(u), tq); });
+      sfor<0, NN>([&](auto K) { tq = fma(tr[HD_K(K)], bc<HD_K(K)>(uv), tq); });
       sd = tq * msk;
     }
     lds_fence();
-    // ZT = U^-1 (L^-1 T); record (M layout: rows h + 4m, column c); A <- R + T (A ZT);
-    // then A's rows to the team layout
+    // ZT = U^-1 (L^-1 T); record (M layout: rows h + 4q, column c); A <- R + T (A ZT);
+    // then A to S0 in team rows
     {
       double li[4][4], x1[4][4], zm[4][4], pm[4][4];
+      auto store_zt = [&] {
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+          const auto zr = Path::rec(A.bsub, B::size, lc, np, um[tt]);
+          const bool ok = grp * 4 + tt < npb;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int r = h + 4 * q;
+            const bool own = ok && r < NN && c < NN;
+            if constexpr (Path::kSink)
+              rec_st<Path::kNT>(own ? zr + (B::Z + r * NN + c) : A.sink + lane, zm[tt][q]);
+            else if (own)
+              zr[B::Z + r * NN + c] = zm[tt][q];
+          }
+        }
+      };
+      if constexpr (!Path::kResident) load_m(O::T, tm);
       get_m(S0, h, c, li);
       mprod<false>(li, tm, x1, h, c);  // L^-1 T
       get_m(S1, h, c, li);
       mprod<false>(li, x1, zm, h, c);  // ZT = U^-1 (L^-1 T)
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        double* zr = A.bsub + ((size_t)lc * nsc + slm[tt]) * ne2;
-        const bool ok = grp * 4 + tt < A.nsc;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const int r = h + 4 * m;
-          if (ok && r < NN && c < NN) zr[r * NN + c] = zm[tt][m];
-        }
-      }
+      // !kResident: the second reads of T~ and R~ and tau' go out before ZT's stores: a
+      // load issued after a store also waits for that store to retire (one in-order
+      // memory counter), so read after them each waited out 16 store round trips
+      const double taul = rec[O::Tau];
+      if constexpr (Path::kResident) store_zt();
       mprod<false>(ram, zm, pm, h, c);  // A ZT   (A symmetric: its own transpose)
+      if constexpr (!Path::kResident) load_m(O::T, tm);
       mprod<false>(tm, pm, ram, h, c);  // T (A ZT)
+      if constexpr (!Path::kResident) {
+        load_m(O::R, rm);
+        store_zt();
+      }
 #pragma unroll
       for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) ram[tt][m] += rm[tt][m];
+        for (int q = 0; q < 4; ++q) ram[tt][q] += rm[tt][q];
       lds_fence();
       put_m(S0, h, c, ram);
       lds_fence();
+      tauc += taul;
     }
-    get_rows<NN>(S0, t, i, ra);
-    sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
-    tauc += rec[2 * NN * NN + 2 * NN];
+    if constexpr (Path::kResident) {
+      get_rows<NN>(S0, t, i, ra);
+      sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
+    }
   }
 
   // ---- Lambertian surface: I+ = g x ----
-  double rgrow = 0.0;
-  sfor<0, NN>([&](auto J) { rgrow = fma(ra[HD_K(J)], Qc.g[HD_K(J)], rgrow); });
-  const double gsd = bc<0>(team_sum(g_i * sd));
-  const double grg = bc<0>(team_sum(g_i * rgrow));
-  double esurf = (1.0 - alb) * bsurf;
-  const double dirsurf = f0mu0 * beam_at(L, tauc);
-  if (beam) esurf += alb * dirsurf / kPi;
-  const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
+  if constexpr (!Path::kResident) {
+    get_rows<NN>(S0, t, i, ra);
+    sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
+  }
+  double dirsurf = 0.0;  // direct beam at the surface (a flux path adds it to F_dn)
+  double rgrow;
+  const double x = team_lambert<NN>(ra, Qc, g_i, sd, alb, [&] {
+    double esurf = (1.0 - alb) * bsurf;
+    if constexpr (Path::kModes) {
+      if (beam) esurf += alb * f0mu0 * exp(-tauc * rmu0) / kPi;
+    } else {
+      dirsurf = f0mu0 * beam_at(L, tauc);
+      if (beam) esurf += alb * dirsurf / kPi;
+    }
+    return esurf;
+  }, rgrow);
   double ip = g_i * x;
-  double* fo = FLX ? nullptr : A.flux + (size_t)(A.flux_local ? (long)sl : s) * (L + 1) * 2;
   double chk = 0.0;
-  // FLX: the level's eight components (team lane 0 stores them)
-  auto emit8 = [&](int lc, double up, double dn, double hu, double hdn) {
-    const size_t nl = (size_t)(L + 1) * nsc;
-    const int lev = L - lc;
-    const double rfldir = F->lvl[(size_t)lc * nsc + sl];
-    const double uavgso = F->lvl[nl + (size_t)lc * nsc + sl];
-    const double absl = F->lvl[2 * nl + (size_t)lc * nsc + sl];
-    const double bl = A.planck ? A.planckv[(size_t)lev * nsc + sl] : 0.0;
-    const double uavgup = 0.5 * hu, uavgdn = 0.5 * hdn;
-    const double uavg = uavgup + uavgdn + uavgso;
-    if (i == 0 && valid) {
-      double* o = F->flx + ((size_t)s * (L + 1) + lev) * kNFlx;
-      o[kFlxRfldir] = rfldir;
-      o[kFlxRfldn] = dn - rfldir;
-      o[kFlxFlup] = up;
-      o[kFlxDfdt] = absl * (uavg - bl);
-      o[kFlxUavg] = uavg;
-      o[kFlxUavgdn] = uavgdn;
-      o[kFlxUavgup] = uavgup;
-      o[kFlxUavgso] = uavgso;
+  // ---- what the upward pass emits at a level: I+- / g to lev (kModes), the eight
+  // components of hd_solve_flx (kFlx; team lane 0 stores them) or the two fluxes ----
+  double* fo = nullptr;
+  if constexpr (!Path::kModes && !Path::kFlx)
+    fo = A.flux + (size_t)(A.flux_local ? (long)sl : s) * (L + 1) * 2;
+  auto emit_lev = [&](int lc, double up, double dn) {  // kModes
+    if constexpr (Path::kModes) {
+      double* lv = A.lev + (size_t)lc * RadLev<NN>::size * np;
+      if (wr) {
+        lv[(size_t)(RadLev<NN>::Ip + i) * np + u] = up;
+        lv[(size_t)(RadLev<NN>::Im + i) * np + u] = dn * rg_i;
+      }
     }
   };
-  {
+  auto emit8 = [&](int lc, double up, double dn, double hu, double hdn) {  // kFlx (a flux path: np == ns)
+    if constexpr (Path::kFlx) {
+      const size_t nl = (size_t)(L + 1) * np;
+      const int lev = L - lc;
+      const double rfldir = F->lvl[(size_t)lc * np + sl];
+      const double uavgso = F->lvl[nl + (size_t)lc * np + sl];
+      const double absl = F->lvl[2 * nl + (size_t)lc * np + sl];
+      const double bl = A.planck ? A.planckv[(size_t)lev * np + sl] : 0.0;
+      const double uavgup = 0.5 * hu, uavgdn = 0.5 * hdn;
+      const double uavg = uavgup + uavgdn + uavgso;
+      if (i == 0 && valid) {
+        double* o = F->flx + ((size_t)s * (L + 1) + lev) * kNFlx;
+        o[kFlxRfldir] = rfldir;
+        o[kFlxRfldn] = dn - rfldir;
+        o[kFlxFlup] = up;
+        o[kFlxDfdt] = absl * (uavg - bl);
+        o[kFlxUavg] = uavg;
+        o[kFlxUavgdn] = uavgdn;
+        o[kFlxUavgup] = uavgup;
+        o[kFlxUavgso] = uavgso;
+      }
+    }
+  };
+  if constexpr (Path::kModes) {
+    double dn = sd;
+    sfor<0, NN>([&](auto J) { dn = fma(ra[HD_K(J)], bc<HD_K(J)>(ip), dn); });
+    emit_lev(L, x, dn);
+    chk += dn * msk;
+  } else {
     const double up = team_sum(g_i * ip);
     const double dn = team_sum(g_i * fma(rgrow, x, sd));
-    if constexpr (FLX) {
+    if constexpr (Path::kFlx) {
       const double hu = team_sum(h_i * ip);
       const double hdn = team_sum(h_i * fma(rgrow, x, sd));
       emit8(L, twopi * up, twopi * dn + dirsurf, hu, hdn);
@@ -1145,354 +1403,76 @@ __device__ __forceinline__ void team_mfma_sweep_body(const SweepArgs& A, const F
   }
   // ---- back-substitution bottom -> top ----
   for (int lc = L - 1; lc >= 0; --lc) {
-    const double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2;
-    double nip = bp[NN * NN + ii] * msk;
+    const auto bp = Path::rec((const double*)A.bsub, B::size, lc, np, u);
+    double nip = bp[B::Tv + ii] * msk;
     sfor<0, NN>([&](auto J) {
-      const double z = bp[ii * NN + HD_K(J)] * msk;
+      const double z = bp[B::Z + ii * NN + HD_K(J)] * msk;
       nip = fma(z, bc<HD_K(J)>(ip), nip);
     });
-    const double rc = bp[NN * NN + NN + ii] * msk;
-    const double up = team_sum(g_i * nip);
-    const double dn = team_sum(rc * nip);
-    ip = nip;
-    if constexpr (FLX) {
-      const double rh = bp[NN * NN + 2 * NN + 1 + ii] * msk;
-      const double hu = team_sum(h_i * nip);
-      const double hdn = bp[NN * NN + 3 * NN + 1] + team_sum(rh * nip);
-      emit8(lc, twopi * up, bp[NN * NN + 2 * NN] + dn, hu, hdn);
-      chk += hu + hdn;
-    } else if (i == 0 && valid) {
-      const int lev = L - lc;
-      fo[2 * lev] = twopi * up;
-      fo[2 * lev + 1] = bp[NN * NN + 2 * NN] + dn;
+    if constexpr (Path::kModes) {
+      ip = nip;
+      double dn = bp[B::Sd + ii] * msk;
+      sfor<0, NN>([&](auto J) {
+        const double r = bp[B::Ra + sym_index<NN>(ii, HD_K(J))] * msk;
+        dn = fma(r, bc<HD_K(J)>(ip), dn);
+      });
+      emit_lev(lc, ip * rg_i, dn);
+      chk += ip + dn;
+    } else {
+      const double rc = bp[B::Rc + ii] * msk;
+      const double up = team_sum(g_i * nip);
+      const double dn = team_sum(rc * nip);
+      ip = nip;
+      if constexpr (Path::kFlx) {
+        const double rh = bp[B::Rh + ii] * msk;
+        const double hu = team_sum(h_i * nip);
+        const double hdn = bp[B::Ch] + team_sum(rh * nip);
+        emit8(lc, twopi * up, bp[B::Cs] + dn, hu, hdn);
+        chk += hu + hdn;
+      } else if (i == 0 && valid) {
+        const int lev = L - lc;
+        fo[2 * lev] = twopi * up;
+        fo[2 * lev + 1] = bp[B::Cs] + dn;
+      }
+      chk += twopi * up + dn;
     }
-    chk += twopi * up + dn;
   }
-  if (!isfinite(chk)) st |= kStNonFinite;
+  if ((!Path::kModes || act) && !isfinite(chk)) st |= kStNonFinite;
   if (valid && st) {
     atomicOr(&A.status[s], st);
     if (st & 0x0F) atomicOr(A.anyerr, 1);
   }
 }
-
-// hd_solve_flx's team sweep
+// hd_solve_flx's team sweep.  One wave per SIMD, as the spher and radiance sweeps
 template <int NN>
 __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
   __shared__ double lds[2 * kSet];
-  team_mfma_sweep_body<NN, true>(A, &F, lds);
+  team_sweep_body<NN, FluxSweepPath<true, false>>(A, &F, nullptr, lds);
 }
-// hd_solve_spher / hd_solve_flx_spher: the one-wave team sweep with the pseudo-spherical beam
+// hd_solve_spher / hd_solve_flx_spher: the team sweep with the pseudo-spherical beam
 template <int NN, bool FLX>
 __global__ __launch_bounds__(64, 1) void hd_team_mfma_sweep_spher_kernel(SweepArgs A, FlxArgs F,
                                                                          SphArgs P) {
   __shared__ double lds[2 * kSet];
-  team_mfma_sweep_body<NN, FLX, true>(A, &F, lds, &P);
+  team_sweep_body<NN, FluxSweepPath<FLX, true>>(A, &F, &P, lds);
 }
-
-
-// ============================================================================
-// K2 (team, MFMA), lean: the same sweep and back-substitution as
-// team_mfma_sweep_body in at most 256 registers, so that two waves share a
-// SIMD (and one can run beside a 240-register layer-kernel wave) instead of one.
-// What changes is only where the operands live between their uses:
-//   * A's team rows (for the level's rc, and u = A t1 + Sd) stay in LDS tile set
-//     S0 from the end of one layer to the middle of the next, not in registers;
-//     W1 = I - R A goes through tile set S1 instead;
-//   * R~ and T~ are read from the layer record where they are needed -- R~ (M
-//     layout) for W1 and again for A <- R~ + T~ (A ZT), R~'s team row for v1, T~'s
-//     team row for Sd, T~ (M layout) for the ZT products -- instead of all at the
-//     top of the layer (second reads of a record are L2 hits);
-//   * per-element record offsets are recomputed where they are used (laundered
-//     lane indices), not hoisted out of the layer loop.
-// The arithmetic and its order are team_mfma_sweep_body's, so the records and fluxes
-// are bitwise the same (profiles/r06/parity/pytest_ab.log: the last run against
-// hd_solve's one-wave sweep, at 31f114a).
-// ============================================================================
+// hd_solve / hd_solve_band (the C5 sweep): two waves per SIMD; NT for a large chunk
 template <int NN, bool NT>
 __global__ __launch_bounds__(64, 2) void hd_team_mfma_sweep_lean_kernel(SweepArgs A) {
   __shared__ double lds[2 * kSet];
-  double* S0 = lds;
-  double* S1 = lds + kSet;
-  const Quad<NN>& Qc = tquad<NN>(c_qt);
-  const int lane = (int)threadIdx.x;
-  const int h = lane >> 4, c = lane & 15;  // M layout
-  const int t = h, i = c;                  // T layout: team t, row i
-  const bool act = i < NN;
-  const int ii = act ? i : 0;
-  const int grp = (int)blockIdx.x;
-  const bool valid = grp * 4 + t < A.nsc;
-  const int sl = valid ? grp * 4 + t : grp * 4;
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-  const int L = A.nlyr;
-  const size_t nsc = A.nsc;
-  int st = 0;
-  const double msk = act ? 1.0 : 0.0;
-  const double g_i = Qc.g[ii] * msk;
-
-  for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;  // A = 0 in S0
-  lds_fence();
-
-  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
-  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
-  const double alb = A.albedo ? A.albedo[s] : 0.0;
-  if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
-  double top = A.fisot ? A.fisot[s] : 0.0;
-  double bsurf = 0.0;
-  if (A.planck) {
-    bsurf = A.planckv[(size_t)(L + 1) * nsc + sl];
-    top += A.planckv[(size_t)(L + 2) * nsc + sl];
-  }
-  const double twopi = 2.0 * kPi;
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
-  const double f0mu0 = beam ? fb * mu0 : 0.0;
-  const int g0 = grp * 4;  // the wave's first solve (uniform)
-
-  // problem tt's record element (r, c) of the matrix at offset off, M layout
-  auto load_m = [&](int lc, int off, double (&x)[4][4]) {
-    __builtin_amdgcn_sched_barrier(0);  // issued here, not hoisted into an earlier phase
-    int hl = h, cl = c;
-    asm volatile("" : "+v"(hl), "+v"(cl));
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int slt = g0 + tt < A.nsc ? g0 + tt : g0;
-      const double* rt = A.scr + ((size_t)lc * nsc + slt) * ne1t<NN>() + off;
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int r = hl + 4 * m;
-        const bool in = r < NN && cl < NN;
-        x[tt][m] = in ? rt[in ? r * NN + cl : 0] : 0.0;
-      }
-    }
-  };
-  // this problem's team row of the matrix at offset off
-  auto load_row = [&](const double* rec, int off, double (&x)[NN]) {
-    __builtin_amdgcn_sched_barrier(0);
-    int il = ii;
-    asm volatile("" : "+v"(il));
-    sfor<0, NN>([&](auto J) { x[HD_K(J)] = rec[off + il * NN + HD_K(J)] * msk; });
-  };
-
-  double ram[4][4];  // A (M layout)
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-    for (int m = 0; m < 4; ++m) ram[tt][m] = 0.0;
-  double sd = g_i * top;
-  double tauc = 0.0;
-
-  for (int lc = 0; lc < L; ++lc) {
-    // the lane indices, laundered per layer: every lane-dependent constant below
-    // (identity entries, triangle masks) is then formed where it is used instead
-    // of all being hoisted out of the loop into live (and spilled) registers
-    int i_ = i, h_ = h, c_ = c;
-    asm volatile("" : "+v"(i_), "+v"(h_), "+v"(c_));
-    const int i = i_, h = h_, c = c_;
-    const double* rec = A.scr + ((size_t)lc * nsc + sl) * ne1t<NN>();
-    double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2t<NN>();
-    double* bw = (act && valid) ? bp : A.sink;
-    // direct beam at the layer top; a unit-beam record's sources scale with it
-    const double eb = exp(-tauc * rmu0);
-    const double sscale = A.beam_scale ? eb : 1.0;
-    const double spl = rec[2 * NN * NN + ii] * msk * sscale;
-
-    // level lc (top of layer lc): F_dn = rc . I+ + cs; A's row i from S0
-    {
-      double ar[NN];
-      get_rows<NN>(S0, t, i, ar);
-      double tq = 0.0;
-      sfor<0, NN>([&](auto J) { tq = fma(ar[HD_K(J)] * msk, Qc.g[HD_K(J)], tq); });
-      bw[NN * NN + NN + ii] = twopi * tq;
-      const double cs = team_sum(g_i * sd);
-      if (i == 0 && valid) bp[NN * NN + 2 * NN] = fma(twopi, cs, f0mu0 * eb);
-    }
-    // W1 = I - R A on the matrix core, to team rows through S1
-    double w[NN];
-    {
-      double rm[4][4], pw[4][4];
-      load_m(lc, 0, rm);
-      mprod<false>(rm, ram, pw, h, c);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) pw[tt][m] = (h + 4 * m == c ? 1.0 : 0.0) - pw[tt][m];
-      lds_fence();
-      put_m(S1, h, c, pw);
-      lds_fence();
-    }
-    get_rows<NN>(S1, t, i, w);
-    sfor<0, NN>([&](auto J) { w[HD_K(J)] *= msk; });
-    // t1 = R Sd + S+ (R's team row read here)
-    double t1 = spl;
-    {
-      double rl[NN];
-      load_row(rec, 0, rl);
-      sfor<0, NN>([&](auto K) { t1 = fma(rl[HD_K(K)], bc<HD_K(K)>(sd), t1); });
-    }
-    // LU without pivoting; reciprocal pivots on the diagonal
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double piv = bc<k>(w[k]);
-      if (!(fabs(piv) > 1.0e-12)) st |= kStPivot;
-      const double rp = rcp_nr(piv);
-      const double lik = w[k] * rp;
-      const double mm = i > k ? lik : 0.0;
-      w[k] = i == k ? rp : (i > k ? lik : w[k]);
-      sfor<k + 1, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        w[j] = fma(-mm, bc<k>(w[j]), w[j]);
-      });
-      pin<NN>(w);  // this step's broadcasts stay in this step
-    });
-    // t1 <- W1^-1 t1
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double tk = bc<k>(t1);
-      if (i > k) t1 = fma(-w[k], tk, t1);
-    });
-    sfor_rev<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      if (i == k) t1 *= w[k];
-      const double tk = bc<k>(t1);
-      if (i < k) t1 = fma(-w[k], tk, t1);
-    });
-    // u = A t1 + Sd (A's row i from S0)
-    double u = sd;
-    {
-      double ar[NN];
-      get_rows<NN>(S0, t, i, ar);
-      sfor<0, NN>([&](auto K) { u = fma(ar[HD_K(K)] * msk, bc<HD_K(K)>(t1), u); });
-    }
-    bw[NN * NN + ii] = t1;
-    // columns of L^-1 and U^-1 from the LU rows (team_mfma_sweep_body)
-    {
-      double zl[NN], zu[NN];
-      sfor<0, NN>([&](auto R) {
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<0, r>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zl[HD_K(K)], v); });
-        zl[r] = v;
-        pin<NN>(w);
-      });
-      sfor_rev<0, NN>([&](auto R) {
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<r + 1, NN>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zu[HD_K(K)], v); });
-        zu[r] = v * bc<r>(w[r]);
-        pin<NN>(w);
-      });
-      sfor<0, NN>([&](auto J) {
-        zl[HD_K(J)] *= msk;
-        zu[HD_K(J)] *= msk;
-      });
-      lds_fence();
-      put_rows<NN>(S0, t, i, zl);  // L^-T, row-major (A's rows in S0 are done)
-      put_rows<NN>(S1, t, i, zu);  // U^-T, row-major
-    }
-    // Sd <- T u + S- (T's team row read here)
-    {
-      double tr[NN];
-      load_row(rec, NN * NN, tr);
-      double tq = rec[2 * NN * NN + NN + ii] * msk * sscale;
-      sfor<0, NN>([&](auto K) { tq = fma(tr[HD_K(K)], bc<HD_K(K)>(u), tq); });
-      sd = tq * msk;
-    }
-    lds_fence();
-    // ZT = U^-1 (L^-1 T); record; A <- R + T (A ZT); A's rows to S0 for the next layer
-    {
-      double li[4][4], x1[4][4], zm[4][4];
-      {
-        double tm[4][4];
-        load_m(lc, NN * NN, tm);
-        get_m(S0, h, c, li);
-        mprod<false>(li, tm, x1, h, c);  // L^-1 T
-      }
-      get_m(S1, h, c, li);
-      mprod<false>(li, x1, zm, h, c);  // ZT = U^-1 (L^-1 T)
-      // The second reads of T~ and R~ and tau' go out before ZT's stores: a load
-      // issued after a store also waits for that store to retire (one in-order
-      // memory counter), so read after them each waited out 16 store round trips
-      const double taul = rec[2 * NN * NN + 2 * NN];
-      double pm[4][4];
-      mprod<false>(ram, zm, pm, h, c);  // A ZT   (A symmetric: its own transpose)
-      {
-        double tm[4][4];
-        load_m(lc, NN * NN, tm);
-        mprod<false>(tm, pm, ram, h, c);  // T (A ZT)
-      }
-      double rm[4][4];
-      load_m(lc, 0, rm);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        double* zr = A.bsub + ((size_t)lc * nsc + (g0 + tt < A.nsc ? g0 + tt : g0)) * ne2t<NN>();
-        const bool ok = g0 + tt < A.nsc;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const int r = h + 4 * m;
-          // branch-free: an element the lane does not own goes to the sink
-          rec_st<NT>((ok && r < NN && c < NN) ? zr + r * NN + c : A.sink + lane, zm[tt][m]);
-        }
-      }
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) ram[tt][m] += rm[tt][m];
-      lds_fence();
-      put_m(S0, h, c, ram);
-      lds_fence();
-      tauc += taul;
-    }
-  }
-
-  // ---- Lambertian surface: I+ = g x ----
-  double rgrow = 0.0;
-  {
-    double ar[NN];
-    get_rows<NN>(S0, t, i, ar);
-    sfor<0, NN>([&](auto J) { rgrow = fma(ar[HD_K(J)] * msk, Qc.g[HD_K(J)], rgrow); });
-  }
-  const double gsd = bc<0>(team_sum(g_i * sd));
-  const double grg = bc<0>(team_sum(g_i * rgrow));
-  double esurf = (1.0 - alb) * bsurf;
-  const double dirsurf = f0mu0 * exp(-tauc * rmu0);
-  if (beam) esurf += alb * dirsurf / kPi;
-  const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
-  double ip = g_i * x;
-  double* fo = A.flux + (size_t)(A.flux_local ? (long)sl : s) * (L + 1) * 2;
-  double chk = 0.0;
-  {
-    const double up = team_sum(g_i * ip);
-    const double dn = team_sum(g_i * fma(rgrow, x, sd));
-    if (i == 0 && valid) {
-      fo[0] = twopi * up;
-      fo[1] = twopi * dn + dirsurf;
-    }
-    chk += twopi * up + twopi * dn;
-  }
-  // ---- back-substitution bottom -> top ----
-  for (int lc = L - 1; lc >= 0; --lc) {
-    const double* bp = A.bsub + ((size_t)lc * nsc + sl) * ne2t<NN>();
-    double nip = bp[NN * NN + ii] * msk;
-    sfor<0, NN>([&](auto J) {
-      const double z = bp[ii * NN + HD_K(J)] * msk;
-      nip = fma(z, bc<HD_K(J)>(ip), nip);
-    });
-    const double rc = bp[NN * NN + NN + ii] * msk;
-    const double up = team_sum(g_i * nip);
-    const double dn = team_sum(rc * nip);
-    ip = nip;
-    if (i == 0 && valid) {
-      const int lev = L - lc;
-      fo[2 * lev] = twopi * up;
-      fo[2 * lev + 1] = bp[NN * NN + 2 * NN] + dn;
-    }
-    chk += twopi * up + dn;
-  }
-  if (!isfinite(chk)) st |= kStNonFinite;
-  if (valid && st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
+  team_sweep_body<NN, LeanSweepPath<NT>>(A, nullptr, nullptr, lds);
+}
+// The intensity path's sweep: four units (solve, azimuthal mode) per wave, the stack
+// state R_above / S_down and I+- kept at every level.  rsw and bsub are unit-contiguous
+// at these sizes ([layer][unit][element]: a team's loads and stores of one unit's
+// record hit neighbouring lines, where the unit-fastest layout the one-lane kernels
+// use put every lane on its own line); lev keeps the unit-fastest layout the per-lane
+// kernels read.  Replaced a one-lane-per-unit loop whose 16 x 16 matrices lived in
+// private memory (62% of the nstr-32 radiance time, profiles/r03/).
+template <int NN>
+__global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
+  __shared__ double lds[2 * kSet];
+  team_sweep_body<NN, RadSweepPath>(A, nullptr, nullptr, lds);
 }
 
 // ============================================================================
@@ -1512,273 +1492,6 @@ __global__ __launch_bounds__(64, 2) void hd_rad_team_layer_kernel(RadArgs A) {
   team_layer_body<NN, RadLayerPath>(A, nullptr, lds);
 }
 
-// ============================================================================
-// Intensity path, nstr 18..32: hd_rad.hip's per-unit adding sweep +
-// back-substitution (hd_rad_sweep_kernel: the stack state R_above/S_down and
-// I+/I- kept at every level) on the team layout with the dense products on the
-// matrix core -- four units (solve, azimuthal mode) per wave, the arithmetic of
-// team_mfma_sweep_body above.  The layer-operator and back-substitution
-// records (rsw, bsub) are unit-contiguous at these sizes ([layer][unit][element]:
-// a team's loads and stores of one unit's record hit neighbouring lines, where the
-// unit-fastest layout the one-lane kernels use put every lane on its own line);
-// lev keeps the unit-fastest layout the per-lane kernels read.  Replaces a
-// one-lane-per-unit loop whose 16 x 16 matrices lived in private memory
-// (62% of the nstr-32 radiance time, profiles/r03/).
-// ============================================================================
-template <int NN>
-__global__ __launch_bounds__(64, 1) void hd_rad_team_sweep_kernel(RadArgs A) {
-  __shared__ double lds[2 * kSet];
-  double* S0 = lds;
-  double* S1 = lds + kSet;
-  const Quad<NN>& Qc = tquad<NN>(c_qt);
-  using O = RadOps<NN>;
-  using B = RadBsub<NN>;
-  constexpr int NE1 = O::size;
-  constexpr int NB = B::size;
-  const int lane = (int)threadIdx.x;
-  const int h = lane >> 4, c = lane & 15;  // M layout
-  const int t = h, i = c;                  // T layout: team t, row i
-  const bool act = i < NN;
-  const int ii = act ? i : 0;
-  const int grp = (int)blockIdx.x;
-  // every lane takes part in the MFMA / LDS / DPP exchanges: a team past the end
-  // repeats the block's first unit and stores nothing
-  const bool valid = grp * 4 + t < A.nu;
-  const int u = valid ? grp * 4 + t : grp * 4;
-  const int m = u / A.ns;
-  const int sl = u - m * A.ns;
-  const long s = A.s0 + sl;
-  const int L = A.nlyr;
-  const size_t nu = A.nu;
-  int st = 0;
-  const double msk = act ? 1.0 : 0.0;
-  const double g_i = Qc.g[ii] * msk;
-  const double rg_i = Qc.rg[ii] * msk;
-  const bool wr = valid && act;
-
-  for (int k = lane; k < 2 * kSet; k += 64) lds[k] = 0.0;
-  lds_fence();
-
-  const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
-  const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
-  double alb = A.albedo ? A.albedo[s] : 0.0;
-  if (!(alb >= 0.0) || !(alb <= 1.0)) st |= kStBadInput;
-  double top = A.fisot ? A.fisot[s] : 0.0;
-  double bsurf = 0.0;
-  if (A.planck) {
-    bsurf = A.planckv[(size_t)(L + 1) * A.ns + sl];
-    top += A.planckv[(size_t)(L + 2) * A.ns + sl];
-  }
-  if (m > 0) alb = top = bsurf = 0.0;  // Lambert surface, isotropic top: mode 0 only
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
-  const double f0mu0 = (beam && m == 0) ? fb * mu0 : 0.0;
-
-  int um[4];  // the wave's four units (M layout)
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt) um[tt] = grp * 4 + tt < A.nu ? grp * 4 + tt : grp * 4;
-
-  double ram[4][4];  // R_above (M layout)
-  double ra[NN];     // R_above row i (T layout)
-  double sd = g_i * top;
-#pragma unroll
-  for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ram[tt][q] = 0.0;
-  sfor<0, NN>([&](auto J) { ra[HD_K(J)] = 0.0; });
-  double tauc = 0.0;
-
-  for (int lc = 0; lc < L; ++lc) {
-    const double* lp = A.rsw + (size_t)lc * NE1 * nu;  // element e of unit v: lp[v*NE1 + e]
-    double* bp = A.bsub + (size_t)lc * NB * nu;
-    // the stack above this layer: R_above (packed upper, row i from j = i) and S_down
-    {  // branch-free: the elements a lane does not own go to the sink
-      double* urow = bp + (size_t)u * NB + B::Ra + sym_index<NN>(ii, ii) - ii;
-      sfor<0, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        double* dst = (wr && j >= i) ? urow + j : A.sink + lane;
-        *dst = ra[j];
-      });
-      *(wr ? bp + (size_t)u * NB + B::Sd + i : A.sink + lane) = sd;
-    }
-    // R~, T~ (packed upper) of the four units in M layout; this unit's rows (T layout)
-    double rm[4][4], tm[4][4];
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = h + 4 * q;
-        const bool in = r < NN && c < NN;
-        const int e = in ? sym_index<NN>(r, c) : 0;
-        rm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + O::R + e] : 0.0;
-        tm[tt][q] = in ? lp[(size_t)um[tt] * NE1 + O::T + e] : 0.0;
-      }
-    double rl[NN], tr[NN];
-    sfor<0, NN>([&](auto J) {
-      const int e = sym_index<NN>(ii, HD_K(J));
-      rl[HD_K(J)] = lp[(size_t)u * NE1 + O::R + e] * msk;
-      tr[HD_K(J)] = lp[(size_t)u * NE1 + O::T + e] * msk;
-    });
-    const double spl = lp[(size_t)u * NE1 + O::Sp + ii] * msk;
-    const double sml = lp[(size_t)u * NE1 + O::Sm + ii] * msk;
-    // W1 = I - R A on the matrix core, to team rows through LDS
-    {
-      double pw[4][4];
-      mprod<false>(rm, ram, pw, h, c);
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) pw[tt][q] = (h + 4 * q == c ? 1.0 : 0.0) - pw[tt][q];
-      lds_fence();
-      put_m(S0, h, c, pw);
-      lds_fence();
-    }
-    double w[NN];
-    get_rows<NN>(S0, t, i, w);
-    sfor<0, NN>([&](auto J) { w[HD_K(J)] *= msk; });
-    // t1 = R Sd + S+
-    double t1 = spl;
-    sfor<0, NN>([&](auto K) { t1 = fma(rl[HD_K(K)], bc<HD_K(K)>(sd), t1); });
-    // LU without pivoting; reciprocal pivots on the diagonal
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double piv = bc<k>(w[k]);
-      if (!(fabs(piv) > 1.0e-12)) st |= kStPivot;
-      const double rp = rcp_nr(piv);
-      const double lik = w[k] * rp;
-      const double mm = i > k ? lik : 0.0;
-      w[k] = i == k ? rp : (i > k ? lik : w[k]);
-      sfor<k + 1, NN>([&](auto J) {
-        constexpr int j = HD_K(J);
-        w[j] = fma(-mm, bc<k>(w[j]), w[j]);
-      });
-    });
-    // t1 <- W1^-1 t1
-    sfor<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      const double tk = bc<k>(t1);
-      if (i > k) t1 = fma(-w[k], tk, t1);
-    });
-    sfor_rev<0, NN>([&](auto K) {
-      constexpr int k = HD_K(K);
-      if (i == k) t1 *= w[k];
-      const double tk = bc<k>(t1);
-      if (i < k) t1 = fma(-w[k], tk, t1);
-    });
-    // u = A t1 + Sd
-    double uv = sd;
-    sfor<0, NN>([&](auto K) { uv = fma(ra[HD_K(K)], bc<HD_K(K)>(t1), uv); });
-    *(wr ? bp + (size_t)u * NB + B::Tv + i : A.sink + lane) = t1;
-    // ZT = W1^-1 T = U^-1 (L^-1 T): columns of the triangular inverses on the team
-    // (lane i: row i of the transposed inverse), the products on the matrix core
-    {
-      double zl[NN], zu[NN];
-      sfor<0, NN>([&](auto R) {
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<0, r>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zl[HD_K(K)], v); });
-        zl[r] = v;
-        pin<NN>(w);
-      });
-      sfor_rev<0, NN>([&](auto R) {
-        constexpr int r = HD_K(R);
-        double v = i == r ? 1.0 : 0.0;
-        sfor<r + 1, NN>([&](auto K) { v = fma(-bc<r>(w[HD_K(K)]), zu[HD_K(K)], v); });
-        zu[r] = v * bc<r>(w[r]);
-        pin<NN>(w);
-      });
-      sfor<0, NN>([&](auto J) {
-        zl[HD_K(J)] *= msk;
-        zu[HD_K(J)] *= msk;
-      });
-      lds_fence();
-      put_rows<NN>(S0, t, i, zl);  // L^-T
-      put_rows<NN>(S1, t, i, zu);  // U^-T
-    }
-    // Sd <- T u + S-
-    {
-      double tq = sml;
-      sfor<0, NN>([&](auto K) { tq = fma(tr[HD_K(K)], bc<HD_K(K)>(uv), tq); });
-      sd = tq * msk;
-    }
-    lds_fence();
-    {
-      double li[4][4], x1[4][4], zm[4][4], pm[4][4];
-      get_m(S0, h, c, li);
-      mprod<false>(li, tm, x1, h, c);  // L^-1 T
-      get_m(S1, h, c, li);
-      mprod<false>(li, x1, zm, h, c);  // ZT
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt) {
-        const bool ok = grp * 4 + tt < A.nu;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int r = h + 4 * q;
-          const bool own = ok && r < NN && c < NN;
-          *(own ? bp + (size_t)um[tt] * NB + B::Z + r * NN + c : A.sink + lane) = zm[tt][q];
-        }
-      }
-      mprod<false>(ram, zm, pm, h, c);  // A ZT
-      mprod<false>(tm, pm, ram, h, c);  // T (A ZT)
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ram[tt][q] += rm[tt][q];
-      lds_fence();
-      put_m(S0, h, c, ram);
-      lds_fence();
-    }
-    get_rows<NN>(S0, t, i, ra);
-    sfor<0, NN>([&](auto J) { ra[HD_K(J)] *= msk; });
-    tauc += lp[(size_t)u * NE1 + O::Tau];
-  }
-
-  // ---- Lambertian surface (mode 0): I+ = g x ----
-  double rgrow = 0.0;
-  sfor<0, NN>([&](auto J) { rgrow = fma(ra[HD_K(J)], Qc.g[HD_K(J)], rgrow); });
-  const double gsd = bc<0>(team_sum(g_i * sd));
-  const double grg = bc<0>(team_sum(g_i * rgrow));
-  double esurf = (1.0 - alb) * bsurf;
-  if (beam) esurf += alb * f0mu0 * exp(-tauc * rmu0) / kPi;
-  const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
-  double ip = g_i * x;
-  double chk = 0.0;
-  {
-    double dn = sd;
-    sfor<0, NN>([&](auto J) { dn = fma(ra[HD_K(J)], bc<HD_K(J)>(ip), dn); });
-    double* lv = A.lev + (size_t)L * RadLev<NN>::size * nu;
-    if (wr) {
-      lv[(size_t)(RadLev<NN>::Ip + i) * nu + u] = x;
-      lv[(size_t)(RadLev<NN>::Im + i) * nu + u] = dn * rg_i;
-    }
-    chk += dn * msk;
-  }
-  // ---- back-substitution bottom -> top, I+ and I- at every level ----
-  for (int lc = L - 1; lc >= 0; --lc) {
-    const double* bp = A.bsub + (size_t)lc * NB * nu;
-    double nip = bp[(size_t)u * NB + B::Tv + ii] * msk;
-    sfor<0, NN>([&](auto J) {
-      nip = fma(bp[(size_t)u * NB + B::Z + ii * NN + HD_K(J)] * msk, bc<HD_K(J)>(ip), nip);
-    });
-    ip = nip;
-    double dn = bp[(size_t)u * NB + B::Sd + ii] * msk;
-    sfor<0, NN>([&](auto J) {
-      const double r = bp[(size_t)u * NB + B::Ra + sym_index<NN>(ii, HD_K(J))] * msk;
-      dn = fma(r, bc<HD_K(J)>(ip), dn);
-    });
-    double* lv = A.lev + (size_t)lc * RadLev<NN>::size * nu;
-    if (wr) {
-      lv[(size_t)(RadLev<NN>::Ip + i) * nu + u] = ip * rg_i;
-      lv[(size_t)(RadLev<NN>::Im + i) * nu + u] = dn * rg_i;
-    }
-    chk += ip + dn;
-  }
-  if (act && !isfinite(chk)) st |= kStNonFinite;
-  if (valid && st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
-}
 
 hipError_t upload_warm_tables_team(const QuadHost* per_nn) {
   // the host tables (a long-double Jacobi per entry) are built once per process;

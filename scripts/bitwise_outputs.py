@@ -102,6 +102,17 @@ def dump(out_dir):
                     finally:
                         ctx.set_chunk(0)
 
+    # ---- a chunk of at least 4 096 solves on the team path: the nontemporal instantiations
+    # of its layer kernel and sweep (4 099 solves of two layers, a last team of three)
+    for nstr in (18, 32):
+        rng = np.random.default_rng(4099 + nstr)
+        prop, bc, temf = _inputs(rng, 1, 4099, 2, nstr, 1, 1)
+        d = disort(nstr, 2, 1, 4099, 1)
+        st = torch.zeros(4099, dtype=torch.int32, device=dev)
+        save(f"forward_nt_n{nstr}", d.forward(t(prop), tb(bc), t(temf), status=st))
+        save(f"forward_nt_n{nstr}_status", st)
+    del prop, bc, temf
+
     # ---- the smallest call on hd_solve_band's row-major route
     rng = np.random.default_rng(77)
     prop, bc, temf = _inputs(rng, 1, 131073, 4, 4, 0, 1)

@@ -176,6 +176,39 @@ def test_team_flup_bitwise_with_hd_solve(nstr, chunk):
     assert np.array_equal(flx[..., IFLUP], f[..., 0])
 
 
+@pytest.mark.parametrize("nstr", [18, 32])
+def test_team_large_chunk_bitwise_with_small_chunks(nstr):
+    """Team path: a chunk of at least 4 096 solves takes the nontemporal instantiations of
+    the layer kernel and of hd_solve's sweep, a smaller one the plain ones; where a record
+    is kept between the two kernels does not change a bit of it.  4 099 solves of two layers
+    (a last team of three) with a beam and Planck emission, in one chunk and in chunks of
+    1 024: fluxes and status equal bit for bit."""
+    from pyharp_amd import _lib
+    from pyharp_amd.disort import _context
+    nwave, ncol, nlyr = 1, 4099, 2
+    assert _lib.chunk_solves(nstr, nlyr, nwave * ncol, planck=True) == nwave * ncol
+    rng = np.random.default_rng(4099 + nstr)
+    prop, bc = _hg_batch(rng, nwave, ncol, nlyr, nstr)
+    bc.update(btemp=np.full((nwave, ncol), 290.0), ttemp=np.full((nwave, ncol), 160.0),
+              temis=rng.uniform(0.1, 0.9, (nwave, ncol)))
+    temf = np.linspace(285.0, 190.0, nlyr + 1)[None, :] + rng.uniform(-5, 5, (ncol, nlyr + 1))
+    d = _disort(nstr, nlyr, nwave, ncol, planck=True, wl=[200.0], wu=[400.0])
+    p, b, t = _dev(prop, bc, temf)
+    ctx = _context(0)
+    out = []
+    for chunk in (0, 1024):
+        st = torch.zeros(nwave * ncol, dtype=torch.int32, device=p.device)
+        ctx.set_chunk(chunk)
+        try:
+            out.append((d.forward(p, b, t, status=st).cpu().numpy(), st.cpu().numpy()))
+        finally:
+            ctx.set_chunk(0)
+    (f, st), (f2, st2) = out
+    assert np.all(np.isfinite(f)) and np.all(f[..., 0] > 0.0)
+    assert np.array_equal(f, f2)
+    assert np.array_equal(st, st2)
+
+
 # --------------------------------------------------------------------------- #
 # lane / wave / chunk edges: a solve's record does not depend on where it ran
 # --------------------------------------------------------------------------- #
