@@ -89,9 +89,11 @@ extern "C" {
 #define HD_STATUS_RESONANCE 0x10 /* warning: umu0 within 1.5e-8 (relative) of 1/k of a
                                     layer: that layer of this solve was solved for a beam
                                     cosine moved to that distance from 1/k (the flux paths;
-                                    the fluxes move by < 1e-7 of their scale).  The radiance
-                                    and 'spher' paths clamp the one denominator instead
-                                    (within 5e-10) and lose that mode's beam source there */
+                                    the fluxes move by < 1e-7 of their scale).  The 'spher'
+                                    calls do the same with each layer's own beam secant,
+                                    of either sign, in place of 1/umu0.  The radiance
+                                    paths clamp the one denominator instead (within 5e-10)
+                                    and lose that mode's beam source there */
 #define HD_STATUS_PIVOT 0x20     /* warning: tiny pivot in the boundary sweep      */
 #define HD_STATUS_ERROR_MASK 0x0F
 

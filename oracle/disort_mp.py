@@ -18,6 +18,11 @@ digits:
 * the eigenproblem is DISORT's reduced one, (alpha - beta)(alpha + beta), by the QR
   iteration of ``mpmath.eig``; the boundary system is solved dense by LU.
 
+With ``zd`` and ``radius`` the beam is the pseudo-spherical one of DESIGN.md section 3e
+(``tests/spher_ref.py`` is its double restatement): slant depths through spherical shells
+and one secant per layer, formed at ``dps`` digits from the altitudes' doubles.  Without
+them no expression changes.
+
 The record (``rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup, uavgso``) follows the
 definitions of ``tests/flx_ref.py`` / ``include/hdisort.h``.
 """
@@ -117,22 +122,32 @@ def _layer(gl, cmu, cwt, nn, nstr, ylm):
 
 def disort_column(dtauc, ssalb, pmom, nstr, *, umu0=1.0, fbeam=0.0, albedo=0.0, fisot=0.0,
                   planck=False, temper=None, btemp=0.0, ttemp=0.0, temis=0.0, wvnmlo=0.0,
-                  wvnmhi=0.0, dps=50, return_mp=False):
+                  wvnmhi=0.0, dps=50, return_mp=False, zd=None, radius=None, geom=None):
     """One flux-only DISORT solve at ``dps`` digits, cdisort conventions (top -> bottom).
+
+    With ``zd`` (the nlyr+1 level altitudes, bottom -> top as everywhere in the library)
+    and ``radius`` the beam is pseudo-spherical (the model of
+    tests/spher_ref.py): it is attenuated along its true path through the shells, ch' on
+    the delta-M scaled depths and ch on the unscaled ones, and inside layer lc it is one
+    exponential of secant lam_lc = (ch'_{lc+1} - ch'_lc) / dtau'_lc (g(j, j) where dtau'
+    = 0); the phase function keeps the true umu0.  ``geom`` = (chp, lam, ch), doubles in
+    solver order (level / layer 0 = top), is a second beam path solved beside the column's
+    own: its record comes back as ``flx_geom`` (the fixture generator's conditioning check:
+    the slant quantities as evaluated in double against the same at ``dps`` digits).
 
     Returns a dict of float64 arrays over the nlyr+1 levels: the eight record entries by
     name, ``fdn`` = rfldir + rfldn, ``flx`` (nlyr+1, 8), ``scale`` (the magnitude dfdt is
     a difference of, as tests/flx_ref.py).  With ``return_mp`` also ``mp``: the record
-    as mpf lists (for comparisons below double precision) and ``kk``: the layers'
-    eigenvalues.
+    as mpf lists (for comparisons below double precision), ``kk``: the layers'
+    eigenvalues, and ``lam``: the layers' beam secants (1 / umu0 without ``zd``).
     """
     with mp.workdps(dps):
         return _column(dtauc, ssalb, pmom, nstr, umu0, fbeam, albedo, fisot, planck, temper,
-                       btemp, ttemp, temis, wvnmlo, wvnmhi, return_mp)
+                       btemp, ttemp, temis, wvnmlo, wvnmhi, return_mp, zd, radius, geom)
 
 
 def _column(dtauc, ssalb, pmom, nstr, umu0, fbeam, albedo, fisot, planck, temper, btemp,
-            ttemp, temis, wvnmlo, wvnmhi, return_mp):
+            ttemp, temis, wvnmlo, wvnmhi, return_mp, zd=None, radius=None, geom=None):
     dtauc_d = np.atleast_1d(np.asarray(dtauc, np.float64))
     ssalb_d = np.atleast_1d(np.asarray(ssalb, np.float64))
     nlyr = dtauc_d.size
@@ -176,13 +191,27 @@ def _column(dtauc, ssalb, pmom, nstr, umu0, fbeam, albedo, fisot, planck, temper
         pkag = [mpf(0)] * (nlyr + 1)
         bplanck = tplanck = mpf(0)
 
+    # ---- the beam's slant depths at the levels and its secant in every layer ----
+    if (zd is None) != (radius is None):
+        raise ValueError("zd and radius go together")
+    spher = zd is not None
+    if geom is not None and not spher:
+        raise ValueError("geom needs zd and radius")
+    if not spher:  # plane-parallel: the expressions below keep umu0 itself
+        own = ([t / umu0 for t in taucpr], [1 / umu0] * nlyr, [t / umu0 for t in tauc])
+    else:
+        own = _slant(zd, radius, umu0, dtaucp, dt)
+
+    # ---- what does not depend on the beam's path: the layers' eigen-solutions, the
+    #      thermal particular solutions and the boundary-condition matrix ----
     zero = [mpf(0)] * nstr
-    kks, gcs, zbeam, z0s, z1s = [], [], [], [], []
+    kks, gcs, ccs, x0s, z0s, z1s = [], [], [], [], [], []
     p0 = [row[0] for row in _legendre(nstr, [-umu0])]
     for lc in range(nlyr):
         gl = gls[lc]
         cc, kk, gp, gm = _layer(gl, cmu, cwt, nn, nstr, ylm)
         kks.append(kk)
+        ccs.append(cc)
         gc = [[None] * nstr for _ in range(nstr)]
         for i in range(nn):
             for j in range(nn):
@@ -191,16 +220,8 @@ def _column(dtauc, ssalb, pmom, nstr, umu0, fbeam, albedo, fisot, planck, temper
                 gc[i][nn + j] = gm[i][j]
                 gc[nn + i][nn + j] = gp[i][j]
         gcs.append(gc)
-        if beam:
-            x0 = [fbeam / (4 * pi) * sum(ylm[l][i] * gl[l] * p0[l] for l in range(nstr))
-                  for i in range(nstr)]
-            a = [[(1 + cmu_full[i] / umu0 if i == j else 0) - cc[i][j] for j in range(nstr)]
-                 for i in range(nstr)]
-            # no scattering, no beam source: Z = 0 (and the matrix is singular where umu0
-            # is a quadrature node exactly, 0.5 at nstr 2)
-            zbeam.append(_solve(a, x0) if any(v != 0 for v in x0) else zero)
-        else:
-            zbeam.append(zero)
+        x0s.append([fbeam / (4 * pi) * sum(ylm[l][i] * gl[l] * p0[l] for l in range(nstr))
+                    for i in range(nstr)] if beam else zero)
         if planck:
             xr1 = (pkag[lc + 1] - pkag[lc]) / dtaucp[lc] if dtaucp[lc] > 0 else mpf(0)
             xr0 = pkag[lc] - xr1 * taucpr[lc]
@@ -215,99 +236,167 @@ def _column(dtauc, ssalb, pmom, nstr, umu0, fbeam, albedo, fisot, planck, temper
             z0s.append(zero)
             z1s.append(zero)
 
-    def zpart(lc, tau):
-        att = mp.exp(-tau / umu0) if beam else mpf(0)
-        return [z0s[lc][i] + z1s[lc][i] * tau + zbeam[lc][i] * att for i in range(nstr)]
-
     ee = [[mp.exp(-k * dtaucp[lc]) for k in kks[lc]] for lc in range(nlyr)]
     one = [mpf(1)] * nn
 
     def cols(lc, scal):
         return [[gcs[lc][i][j] * scal[j] for j in range(nstr)] for i in range(nstr)]
 
-    def top_cols(lc):
-        return cols(lc, one + ee[lc])
-
-    def bot_cols(lc):
-        return cols(lc, ee[lc] + one)
-
-    # ---- boundary-condition system ----
+    tops = [cols(lc, one + ee[lc]) for lc in range(nlyr)]
+    bots = [cols(lc, ee[lc] + one) for lc in range(nlyr)]
     ncol = nstr * nlyr
     a = mp.matrix(ncol, ncol)
-    b = mp.matrix(ncol, 1)
-    t0 = top_cols(0)
-    zp0 = zpart(0, mpf(0))
     for i in range(nn):
         for j in range(nstr):
-            a[i, j] = t0[nn + i][j]
-        b[i] = fisot + tplanck - zp0[nn + i]
-    tops = [t0] + [top_cols(lc) for lc in range(1, nlyr)]
-    bots = [bot_cols(lc) for lc in range(nlyr)]
+            a[i, j] = tops[0][nn + i][j]
     for lc in range(nlyr - 1):
         r0 = nn + lc * nstr
-        za = zpart(lc + 1, taucpr[lc + 1])
-        zb = zpart(lc, taucpr[lc + 1])
         for i in range(nstr):
             for j in range(nstr):
                 a[r0 + i, lc * nstr + j] = bots[lc][i][j]
                 a[r0 + i, (lc + 1) * nstr + j] = -tops[lc + 1][i][j]
-            b[r0 + i] = za[i] - zb[i]
     r0 = nn + (nlyr - 1) * nstr
     lb = bots[nlyr - 1]
     refl = [2 * albedo * cwt[i] * cmu[i] for i in range(nn)]
-    zb = zpart(nlyr - 1, taucpr[nlyr])
-    rhs = (1 - albedo) * bplanck
-    if beam:
-        rhs += albedo * umu0 * fbeam * mp.exp(-taucpr[nlyr] / umu0) / pi
-    rz = sum(refl[m] * zb[nn + m] for m in range(nn))
     for j in range(nstr):
         rl = sum(refl[m] * lb[nn + m][j] for m in range(nn))
         for i in range(nn):
             a[r0 + i, (nlyr - 1) * nstr + j] = lb[i][j] - rl
-    for i in range(nn):
-        b[r0 + i] = rhs - (zb[i] - rz)
-    ll = list(mp.lu_solve(a, b))
 
-    # ---- the nodes' field at the levels and the record ----
-    uu = []
-    for lev in range(nlyr + 1):
-        lc = max(lev - 1, 0)
-        m = tops[0] if lev == 0 else bots[lc]
-        zp = zp0 if lev == 0 else zpart(lc, taucpr[lev])
-        uu.append([sum(m[i][j] * ll[lc * nstr + j] for j in range(nstr)) + zp[i]
-                   for i in range(nstr)])
-    rec = [[mpf(0)] * NFLX for _ in range(nlyr + 1)]
-    scale = []
-    for lev in range(nlyr + 1):
-        r = rec[lev]
-        up, dn = uu[lev][:nn], uu[lev][nn:]
-        r[IFLUP] = 2 * pi * sum(cwt[i] * cmu[i] * up[i] for i in range(nn))
-        dfdn = 2 * pi * sum(cwt[i] * cmu[i] * dn[i] for i in range(nn))
-        r[IUAVGUP] = sum(cwt[i] * up[i] for i in range(nn)) / 2
-        r[IUAVGDN] = sum(cwt[i] * dn[i] for i in range(nn)) / 2
+    # ---- per beam path: its particular solution, the right-hand side, the record ----
+    def rhs_of(chp, lam):
+        zbeam = []
+        for lc in range(nlyr):
+            # no scattering, no beam source: Z = 0 (and the matrix is singular where umu0
+            # is a quadrature node exactly, 0.5 at nstr 2)
+            if not beam or not any(v != 0 for v in x0s[lc]):
+                zbeam.append(zero)
+                continue
+            m = [[(1 + (cmu_full[i] * lam[lc] if spher else cmu_full[i] / umu0)
+                   if i == j else 0) - ccs[lc][i][j] for j in range(nstr)]
+                 for i in range(nstr)]
+            zbeam.append(_solve(m, x0s[lc]))
+
+        def zpart(lc, tau):
+            if not beam:
+                att = mpf(0)
+            elif spher:
+                att = mp.exp(-(chp[lc] + lam[lc] * (tau - taucpr[lc])))
+            else:
+                att = mp.exp(-tau / umu0)
+            return [z0s[lc][i] + z1s[lc][i] * tau + zbeam[lc][i] * att for i in range(nstr)]
+
+        b = mp.matrix(ncol, 1)
+        zp0 = zpart(0, mpf(0))
+        for i in range(nn):
+            b[i] = fisot + tplanck - zp0[nn + i]
+        for lc in range(nlyr - 1):
+            za = zpart(lc + 1, taucpr[lc + 1])
+            zb = zpart(lc, taucpr[lc + 1])
+            for i in range(nstr):
+                b[nn + lc * nstr + i] = za[i] - zb[i]
+        zb = zpart(nlyr - 1, taucpr[nlyr])
+        rhs = (1 - albedo) * bplanck
         if beam:
-            r[IRFLDIR] = umu0 * fbeam * mp.exp(-tauc[lev] / umu0)
-            sdir = umu0 * fbeam * mp.exp(-taucpr[lev] / umu0)
-            r[IRFLDN] = dfdn + sdir - r[IRFLDIR]
-            r[IUAVGSO] = fbeam * mp.exp(-taucpr[lev] / umu0) / (4 * pi)
-        else:
-            r[IRFLDN] = dfdn
-        r[IUAVG] = r[IUAVGUP] + r[IUAVGDN] + r[IUAVGSO]
-        ssa_in = mpf(float(ssalb_d[max(lev - 1, 0)]))  # the input value, not the dithered
-        absl = (1 - ssa_in) * 4 * pi
-        r[IDFDT] = absl * (r[IUAVG] - pkag[lev])
-        scale.append(absl * max(r[IUAVG], pkag[lev]))
+            rhs += albedo * umu0 * fbeam * mp.exp(-chp[nlyr]) / pi
+        rz = sum(refl[m] * zb[nn + m] for m in range(nn))
+        for i in range(nn):
+            b[r0 + i] = rhs - (zb[i] - rz)
+        return b, zp0, zpart
 
+    def record(chp, ch, ll, zp0, zpart):
+        uu = []
+        for lev in range(nlyr + 1):
+            lc = max(lev - 1, 0)
+            m = tops[0] if lev == 0 else bots[lc]
+            zp = zp0 if lev == 0 else zpart(lc, taucpr[lev])
+            uu.append([sum(m[i][j] * ll[lc * nstr + j] for j in range(nstr)) + zp[i]
+                       for i in range(nstr)])
+        rec = [[mpf(0)] * NFLX for _ in range(nlyr + 1)]
+        scale = []
+        for lev in range(nlyr + 1):
+            r = rec[lev]
+            up, dn = uu[lev][:nn], uu[lev][nn:]
+            r[IFLUP] = 2 * pi * sum(cwt[i] * cmu[i] * up[i] for i in range(nn))
+            dfdn = 2 * pi * sum(cwt[i] * cmu[i] * dn[i] for i in range(nn))
+            r[IUAVGUP] = sum(cwt[i] * up[i] for i in range(nn)) / 2
+            r[IUAVGDN] = sum(cwt[i] * dn[i] for i in range(nn)) / 2
+            if beam:
+                r[IRFLDIR] = umu0 * fbeam * mp.exp(-ch[lev])
+                sdir = umu0 * fbeam * mp.exp(-chp[lev])
+                r[IRFLDN] = dfdn + sdir - r[IRFLDIR]
+                r[IUAVGSO] = fbeam * mp.exp(-chp[lev]) / (4 * pi)
+            else:
+                r[IRFLDN] = dfdn
+            r[IUAVG] = r[IUAVGUP] + r[IUAVGDN] + r[IUAVGSO]
+            ssa_in = mpf(float(ssalb_d[max(lev - 1, 0)]))  # the input value, not the dithered
+            absl = (1 - ssa_in) * 4 * pi
+            r[IDFDT] = absl * (r[IUAVG] - pkag[lev])
+            scale.append(absl * max(r[IUAVG], pkag[lev]))
+        return rec, scale
+
+    paths = [own]
+    if geom is not None:
+        paths.append(tuple([mpf(float(v)) for v in x] for x in geom))
+    parts = [rhs_of(chp, lam) for chp, lam, _ in paths]
+    sols = _lu_solve_each(a, [pt[0] for pt in parts])
+    recs = [record(chp, ch, list(ll), pt[1], pt[2])
+            for (chp, _, ch), ll, pt in zip(paths, sols, parts)]
+
+    rec, scale = recs[0]
     flx = np.array([[float(v) for v in r] for r in rec])
     out = {"flx": flx, "scale": np.array([float(s) for s in scale]),
            "rfldir": flx[:, IRFLDIR], "rfldn": flx[:, IRFLDN], "flup": flx[:, IFLUP],
            "dfdt": flx[:, IDFDT], "uavg": flx[:, IUAVG], "uavgdn": flx[:, IUAVGDN],
            "uavgup": flx[:, IUAVGUP], "uavgso": flx[:, IUAVGSO],
            "fdn": np.array([float(r[IRFLDIR] + r[IRFLDN]) for r in rec])}
+    if geom is not None:
+        out["flx_geom"] = np.array([[float(v) for v in r] for r in recs[1][0]])
     if return_mp:
         out["mp"] = rec
         out["kk"] = kks
+        out["lam"] = own[1]
     return out
+
+
+def _lu_solve_each(a, bs):
+    """``mp.lu_solve(a, b)`` for every b of ``bs`` with one factorisation: the same
+    arithmetic (ten guard bits, partial pivoting), the O(n^3) part done once."""
+    prec = mp.prec
+    try:
+        mp.prec += 10
+        lu, piv = mp.LU_decomp(a.copy(), overwrite=True)
+        return [mp.U_solve(lu, mp.L_solve(lu, b, piv)) for b in bs]
+    finally:
+        mp.prec = prec
+
+
+def _slant(zd, radius, umu0, dtaucp, dt):
+    """(chp, lam, ch) in solver order (level / layer 0 = top) from the altitudes ``zd``
+    (doubles, bottom -> top): with z_m the levels and layer j between z_j and z_{j+1},
+        g(l, j) = (2R + z_{j+1} + z_j) / (a(l, j+1) + a(l, j)),
+        a(l, m) = sqrt((z_m - z_l)(2R + z_m + z_l) + ((R + z_l) mu0)^2),
+    ch(l) = sum_{j >= l} g(l, j) dtau_j."""
+    z = [mpf(float(v)) for v in np.asarray(zd, np.float64).ravel()]
+    nlyr = len(dt)
+    if len(z) != nlyr + 1:
+        raise ValueError("zd must hold nlyr + 1 levels")
+    r = mpf(float(radius))
+
+    def a(l, m):
+        return mp.sqrt((z[m] - z[l]) * (2 * r + z[m] + z[l]) + ((r + z[l]) * umu0) ** 2)
+
+    def g(l, j):
+        return (2 * r + z[j + 1] + z[j]) / (a(l, j + 1) + a(l, j))
+
+    def slant(d):  # d top -> bottom; harp layer j is solver layer nlyr - 1 - j
+        return [sum((g(l, j) * d[nlyr - 1 - j] for j in range(l, nlyr)), mpf(0))
+                for l in range(nlyr, -1, -1)]
+
+    chp, ch = slant(dtaucp), slant(dt)
+    lam = [(chp[lc + 1] - chp[lc]) / dtaucp[lc] if dtaucp[lc] > 0
+           else g(nlyr - 1 - lc, nlyr - 1 - lc) for lc in range(nlyr)]
+    return chp, lam, ch
 
 
 def layer_eigenvalues(ssa, pmom, nstr, dps=50):
@@ -331,13 +420,15 @@ def layer_eigenvalues(ssa, pmom, nstr, dps=50):
 # harp-level drivers (the contract of disort_np.disort_forward)
 # --------------------------------------------------------------------------- #
 def flx_forward(prop, bc, temf=None, *, nstr, nmom=None, planck=False, wave_lower=None,
-                wave_upper=None, dps=50):
+                wave_upper=None, dps=50, zd=None, radius=None):
     """prop (W, C, L, nprop), layer / level 0 = bottom; bc: dict of (W, C) arrays; temf
-    (C, L+1) bottom -> top.  Returns (flx (W, C, L+1, 8), scale (W, C, L+1))."""
+    (C, L+1) bottom -> top; zd (L+1,) or (C, L+1) bottom -> top with radius: the
+    pseudo-spherical beam.  Returns (flx (W, C, L+1, 8), scale (W, C, L+1))."""
     prop = np.asarray(prop, np.float64)
     nwave, ncol, nlyr, nprop = prop.shape
     nmom = nstr if nmom is None else nmom
     nm = max(0, min(nmom, nprop - 2))
+    zd = None if zd is None else np.asarray(zd, np.float64)
 
     def bcv(key, default):
         if key in bc and bc[key] is not None:
@@ -361,6 +452,8 @@ def flx_forward(prop, bc, temf=None, *, nstr, nmom=None, planck=False, wave_lowe
                 kw = dict(planck=True, temper=np.asarray(temf)[c, ::-1], btemp=v["btemp"][w, c],
                           ttemp=v["ttemp"][w, c], temis=v["temis"][w, c],
                           wvnmlo=wave_lower[w], wvnmhi=wave_upper[w])
+            if zd is not None:
+                kw.update(zd=zd[c] if zd.ndim == 2 else zd, radius=radius)
             r = disort_column(p[:, 0], ssa, pm, nstr, umu0=v["umu0"][w, c],
                               fbeam=v["fbeam"][w, c], albedo=v["albedo"][w, c],
                               fisot=v["fisot"][w, c], dps=dps, **kw)
@@ -375,9 +468,10 @@ def flux_of_record(flx):
 
 
 def disort_forward(prop, bc, temf=None, *, nstr, nmom=None, planck=False, wave_lower=None,
-                   wave_upper=None, dps=50):
+                   wave_upper=None, dps=50, zd=None, radius=None):
     """Batch driver with the contract of ``disort_np.disort_forward``: flux
     (W, C, L+1, 2), level 0 = surface, [..., 0] = upward, [..., 1] = rfldir + rfldn."""
     flx, _ = flx_forward(prop, bc, temf, nstr=nstr, nmom=nmom, planck=planck,
-                         wave_lower=wave_lower, wave_upper=wave_upper, dps=dps)
+                         wave_lower=wave_lower, wave_upper=wave_upper, dps=dps, zd=zd,
+                         radius=radius)
     return flux_of_record(flx)

@@ -106,11 +106,24 @@ constexpr double kResPolish = 3.0e-4;
 // particular solution of a beam at mu0' up to a residual of relative size kResMove in the
 // source, so the flux moves by O(kResMove) and rounding is amplified by 1 / kResMove
 // (profiles/hard/threshold_sweep.txt).  Sets HD_STATUS_RESONANCE.
+// The 'spher' instantiations do the same with the layer's own secant lambda in place of
+// 1/mu0: lambda differs in every layer and may be negative (under a thicker layer), the
+// resonance is at lambda = -k_j too, and the moved secant lambda' = sign(lambda) k_j
+// sqrt(1 +- kResMove) keeps lambda's sign.  lambda' goes where 1/mu0' does, the layer's own
+// transmission exp(-tau' lambda') included; the amplitude at the layer top exp(-ch'_top),
+// the direct beam at every level and the phase function at the true mu0 stay
+// (profiles/spherhard/).
 constexpr double kResMove = 3.0e-8;
-// The clamp the radiance kernels (hd_rad.hip, hd_rad_team_layer_kernel) and the 'spher'
-// instantiations still use: the one denominator held at +-kResClamp / mu0^2 and nothing
-// else moved, which drops that mode's share of the beam source.
+// The clamp the radiance kernels (hd_rad.hip, hd_rad_team_layer_kernel) still use: the one
+// denominator held at +-kResClamp / mu0^2 and nothing else moved, which drops that mode's
+// share of the beam source.
 constexpr double kResClamp = 1.0e-9;
+// 'spher': the beam's transmission through a layer is exp(ch'_top - ch'_bottom), and under a
+// much thicker layer ch' falls through the layer (lambda < 0).  Where it falls by more than
+// kE0Cap the transmission is held at exp(kE0Cap) and the amplitude at the layer top lowered
+// to exp(-(ch'_bottom + kE0Cap)): the amplitude at the bottom, the one that matters, is
+// exact, the top's (below exp(-kE0Cap) of it) merely small, and 0 * inf never forms.
+constexpr double kE0Cap = 600.0;
 // Thin thermal layer: with a Planck source linear in tau the slope part of the source,
 // x = g 2 (dB / tau') h, is O(dB / tau') and Q~- = I - A- is O(tau'): formed as that
 // difference, Q~- x carries an error eps dB / tau' (1e-7 of the flux scale at tau' = 1e-5

@@ -324,7 +324,8 @@ __host__ __device__ constexpr int psi_doubles() {
 // SPHER (pseudo-spherical beam): the beam's secant in this layer
 // is hd_spher_kernel's lambda (any sign, or zero) in place of 1/mu0, its amplitude at the
 // layer top exp(-ch'_top) and its transmission exp(-(ch'_bottom - ch'_top)); the phase
-// function keeps the true mu0
+// function keeps the true mu0.  On a resonance lambda^2 = k_j^2 the layer is solved for
+// the moved secant of hd_device.hpp's kResMove, which keeps lambda's sign
 template <int NN, bool NT, bool SPHER = false>
 __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, int lc,
                                           double* psi_lds, int lt, PairOutT<NT>& out,
@@ -540,6 +541,7 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   // beam, the part that needs only B and k (before L is back: y2 dies first)
   double ybt[NN];  // B K^-1 tt, tt = V^T y2 / (1/mu0^2 - k^2), V = B K^-1
   double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
+  bool moved = false;   // rmu0e is the moved secant, not the beam's own
   if (beam) {
     double tt[NN];
     const double r2 = rmu0 * rmu0;
@@ -549,41 +551,36 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
       double t = 0.0;
 #pragma unroll
       for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
-      double den = fma(-kk[j], kk[j], r2);
-      if constexpr (SPHER) {
-        if (fabs(den) < kResClamp * r2) {
-          st |= kStResonance;
-          den = den < 0.0 ? -kResClamp * r2 : kResClamp * r2;
-        }
-      } else {
-        near = near || fabs(den) < kResMove * r2;
-      }
+      const double den = fma(-kk[j], kk[j], r2);
+      near = near || fabs(den) < kResMove * r2;
       tt[j] = t * (rk[j] * rk[j]) * rcp_nr(den);  // K^-1 (V^T y2 / den)
     }
-    if constexpr (!SPHER) {
-      if (near) {
-        // the mode nearest the resonance sets the secant 1/mu0'^2, and tt is formed again
-        // with it (a second eigenvalue within kResMove of that mode would keep a small
-        // denominator: eigenvalues of a layer that close are not known to occur, and
-        // kStNonFinite would report it)
-        st |= kStResonance;
-        double dmin = 2.0 * r2, r2e = r2;
+    if (near) {
+      // the mode nearest the resonance sets the secant 1/mu0'^2, and tt is formed again
+      // with it (a second eigenvalue within kResMove of that mode would keep a small
+      // denominator: eigenvalues of a layer that close are not known to occur, and
+      // kStNonFinite would report it)
+      st |= kStResonance;
+      moved = true;
+      double dmin = 2.0 * r2, r2e = r2;
 #pragma unroll
-        for (int j = 0; j < NN; ++j) {
-          const double den = fma(-kk[j], kk[j], r2);
-          if (fabs(den) < dmin) {
-            dmin = fabs(den);
-            r2e = kk[j] * kk[j] * (den < 0.0 ? 1.0 - kResMove : 1.0 + kResMove);
-          }
+      for (int j = 0; j < NN; ++j) {
+        const double den = fma(-kk[j], kk[j], r2);
+        if (fabs(den) < dmin) {
+          dmin = fabs(den);
+          r2e = kk[j] * kk[j] * (den < 0.0 ? 1.0 - kResMove : 1.0 + kResMove);
         }
-        rmu0e = sqrt(r2e);
+      }
+      rmu0e = sqrt(r2e);
+      // SPHER: the layer's secant lambda may be negative (under a thicker layer), and the
+      // resonance is at lambda = -k_j too; the move stays on lambda's side of zero
+      if constexpr (SPHER) rmu0e = copysign(rmu0e, rmu0);
 #pragma unroll
-        for (int j = 0; j < NN; ++j) {
-          double t = 0.0;
+      for (int j = 0; j < NN; ++j) {
+        double t = 0.0;
 #pragma unroll
-          for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
-          tt[j] = t * (rk[j] * rk[j]) * rcp_nr(fma(-kk[j], kk[j], r2e));
-        }
+        for (int i = 0; i < NN; ++i) t = fma(v[i][j], y2[i], t);
+        tt[j] = t * (rk[j] * rk[j]) * rcp_nr(fma(-kk[j], kk[j], r2e));
       }
     }
 #pragma unroll
@@ -631,10 +628,21 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
     double att;
     if constexpr (SPHER) {
       const double ct = P->chp[(size_t)lc * A.nsc + sl];
-      att = 0.5 * exp(-ct);
+      const double cb = P->chp[(size_t)(lc + 1) * A.nsc + sl];
+      // a layer solved for a moved secant transmits along that secant, as the plain
+      // path's does; any other by the difference of its two slant depths
+      double d = moved ? -taup * rmu0e : ct - cb;
+      // under a much thicker layer the slant depth falls through this one; past kE0Cap
+      // (hd_device.hpp) the transmission is held and the top's amplitude lowered to match
+      double ta = ct;
+      if (taup > 0.0 && d > kE0Cap) {
+        d = kE0Cap;
+        ta = cb + kE0Cap;
+      }
+      att = 0.5 * exp(-ta);
       // a layer of zero depth leaves the diffuse field alone (the beam below it still
       // changes: the sweep takes that from ch' of the next level)
-      e0 = taup > 0.0 ? exp(ct - P->chp[(size_t)(lc + 1) * A.nsc + sl]) : 1.0;
+      e0 = taup > 0.0 ? exp(d) : 1.0;
     } else {
       const double tauc = A.tauc ? A.tauc[(size_t)lc * A.nsc + sl] : 0.0;
       att = 0.5 * exp(-tauc * rmu0);

@@ -236,12 +236,12 @@ __device__ __forceinline__ double team_matvec(const double (&xr)[NN], double x) 
 // layer_body -- hd_spher_kernel's secant lambda in place of 1/mu0, exp(-ch'_top) at
 // the layer top.  kNT: nontemporal R~/T~ stores.  kWarm, kThin and kSecant switch
 // the Jacobi warm start, the thin-thermal-layer form and the resonance secant move
-// (else the kResClamp clamp) -- DESIGN.md sections 3f and 10 item 6.
+// (else the kResClamp clamp, the radiance path's) -- DESIGN.md sections 3f and 10 item 6.
 template <bool NT, bool SPHER>
 struct FluxLayerPath {
   using Args = LayerArgs;
   static constexpr bool kModes = false, kSpher = SPHER, kNT = NT;
-  static constexpr bool kWarm = true, kThin = true, kSecant = !SPHER;
+  static constexpr bool kWarm = true, kThin = true, kSecant = true;
   static __device__ __forceinline__ int problems(const Args& A) { return A.nsc; }
   static __device__ __forceinline__ int solves(const Args& A) { return A.nsc; }
 };
@@ -850,6 +850,7 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
       const double tv = team_matvec<NN>(r_, w2);
       double den = fma(-kk, kk, r2);
       double rmu0e = rmu0;  // 1/mu0', the secant the layer is solved for (kResMove)
+      [[maybe_unused]] bool moved = false;
       if constexpr (!Path::kSecant) {
         if (act && fabs(den) < kResClamp * r2) {
           st |= kStResonance;
@@ -873,7 +874,10 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
           });
           if (r2e != 0.0) {
             st |= kStResonance;
+            moved = true;
             rmu0e = sqrt(r2e);
+            // the pseudo-spherical secant may be negative: the move keeps its sign
+            if constexpr (Path::kSpher) rmu0e = copysign(rmu0e, rmu0);
             den = fma(-kk, kk, r2e);
           }
         }
@@ -885,8 +889,19 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
       const double yy = team_matvec<NN>(r_, sd_i * mu_i * sv);
       double att;
       if constexpr (Path::kSpher) {
+        // as hd_kernels.hip's layer_body: a moved layer transmits along its secant, any
+        // other by the difference of its slant depths, held at kE0Cap with the top's
+        // amplitude lowered to match; a layer of zero depth leaves the diffuse field alone
         const double ct = P->chp[(size_t)lc * ns + sl];
-        att = 0.5 * exp(-ct);
+        const double cb = P->chp[(size_t)(lc + 1) * ns + sl];
+        double d = moved ? -taup * rmu0e : ct - cb;
+        double ta = ct;
+        if (taup > 0.0 && d > kE0Cap) {
+          d = kE0Cap;
+          ta = cb + kE0Cap;
+        }
+        att = 0.5 * exp(-ta);
+        e0 = taup > 0.0 ? exp(d) : 1.0;
       } else {
         // a flux path's tauc may be null: sources for a unit beam at the layer top (the
         // sweep scales them)
@@ -896,12 +911,7 @@ __device__ __forceinline__ void team_layer_body(typename Path::Args A, const Sph
       const double dd = rg_i * fma(-yy, rmu0e, lxd);
       zp = (sv + dd) * att;
       zm = (sv - dd) * att;
-      if constexpr (Path::kSpher) {  // a layer of zero depth leaves the diffuse field alone
-        e0 = taup > 0.0 ? exp(P->chp[(size_t)lc * ns + sl] - P->chp[(size_t)(lc + 1) * ns + sl])
-                        : 1.0;
-      } else {
-        e0 = exp(-taup * rmu0e);
-      }
+      if constexpr (!Path::kSpher) e0 = exp(-taup * rmu0e);
     }
     if constexpr (Path::kModes) {
       if (wr) {

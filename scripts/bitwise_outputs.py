@@ -129,6 +129,17 @@ def dump(out_dir):
         a = (t(prop), tb(bc), t(temf))
         save(f"spher_n{nstr}", d.forward(*a, zd=zd))
         save(f"flx_spher_n{nstr}", d.forward_flx(*a, zd=zd))
+    # a low sun (secants that differ by layer, some negative under the thicker layers) on
+    # altitudes per column, with the status words: no layer here is on a resonance
+    for nstr in (4, 16, 32):
+        rng = np.random.default_rng(4300 + nstr)
+        prop, bc, temf = _inputs(rng, 2, 9, 12, nstr, 1, 1)
+        bc["umu0"] = rng.uniform(0.01, 0.2, (2, 9))
+        zd = t(np.linspace(0.0, 96.0e3, 13)[None, :] * rng.uniform(0.8, 1.2, (9, 1)))
+        d = disort(nstr, 12, 2, 9, 1, flags="lamber,quiet,onlyfl,spher", radius=3.39e6)
+        st = torch.zeros(18, dtype=torch.int32, device=dev)
+        save(f"spher_lowsun_n{nstr}", d.forward(t(prop), tb(bc), t(temf), zd=zd, status=st))
+        save(f"spher_lowsun_n{nstr}_status", st)
 
     # ---- the hard-regime fixture through forward
     fix = hard_cases.load(os.path.join(ROOT, "tests", "golden"))

@@ -36,8 +36,15 @@ from oracle.disort_np import DITHER, double_gauss, legendre_table, plkavg
 # particular solution and the beam's attenuation inside the layer.  RES_CLAMP is the
 # earlier rule (the one denominator clamped at +-1e-9 / mu0^2, nothing else moved), kept
 # for the sweep: it drops that mode's share of the beam source.
+#
+# With the pseudo-spherical beam (``zd``) the layer's secant lambda (any sign) stands where
+# 1/mu0 does, and the move keeps its sign: lambda' = sign(lambda) k_j sqrt(1 +- RES_MOVE).
+# KEEP_SIGN = False is the plain path's rule (sqrt alone) carried over as it stands, kept
+# to show what it costs where lambda < 0 (tests/test_kernel_model.py).
 RES_MOVE = 3.0e-8
 RES_CLAMP = None
+KEEP_SIGN = True
+E0_CAP = 600.0  # hd_device.hpp kE0Cap
 # THIN_TAU: in a layer of scaled depth 0 < tau' < THIN_TAU the slope part of the thermal
 # source, x = g 2 (dB / tau') h, goes through Q~- = A- Omega Omega^T (products only)
 # instead of Q~- = I - A- (a difference of O(1) numbers for an O(tau') result, which under
@@ -46,7 +53,9 @@ RES_CLAMP = None
 THIN_TAU = 1.0e-3
 
 
-def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
+def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top, lam=None, ch=None):
+    """lam, ch (pseudo-spherical beam): the layer's secant in place of 1/mu0 and the slant
+    depths ch' at its top and bottom in place of tauc_top / mu0."""
     nn = nstr // 2
     mu, w = double_gauss(nn)
     if ssa == 1.0:
@@ -103,9 +112,11 @@ def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
     zm = np.zeros(nn)
     e0 = 1.0
     if fbeam > 0 and umu0 > 0:
-        r2 = 1.0 / umu0 ** 2
+        rl = 1.0 / umu0 if lam is None else lam
+        r2 = 1.0 / umu0 ** 2 if lam is None else rl * rl
         den = r2 - k2
-        rmu0 = 1.0 / umu0
+        rmu0 = rl
+        moved = False
         if RES_CLAMP is not None:
             small = np.abs(den) < RES_CLAMP * r2
             den = np.where(small, np.where(den < 0.0, -RES_CLAMP * r2, RES_CLAMP * r2), den)
@@ -114,17 +125,34 @@ def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
             if abs(r2 - k2[j]) < RES_MOVE * r2:
                 r2m = k2[j] * (1.0 - RES_MOVE if r2 < k2[j] else 1.0 + RES_MOVE)
                 rmu0 = math.sqrt(r2m)
+                if lam is not None and KEEP_SIGN:
+                    rmu0 = math.copysign(rmu0, rl)
+                moved = True
                 den = r2m - k2
-        e0 = math.exp(-taup * rmu0)
+        e0_cap = None
+        if lam is None:
+            e0 = math.exp(-taup * rmu0)
+        else:
+            # off resonance the layer's transmission is the difference of its two depths.
+            # Under a much thicker layer the slant depth falls through the layer; where it
+            # falls by more than E0_CAP the transmission is held at exp(E0_CAP) and the
+            # amplitude at the top lowered to match, so that the bottom's, exp(-ch'_bottom),
+            # is right and the top's (below exp(-E0_CAP) of it) is merely small
+            d = 0.0 if not taup > 0.0 else (-taup * rmu0 if moved else ch[0] - ch[1])
+            if d > E0_CAP:
+                d, e0_cap = E0_CAP, math.exp(-((ch[1] if taup > 0.0 else ch[0]) + E0_CAP))
+            e0 = math.exp(d) if taup > 0.0 else 1.0
         p0 = legendre_table(nstr, [umu0])[:, 0]
         xs = fbeam / (2 * math.pi) * (pt[ev].T @ (gl[ev] * p0[ev]))
         xd = -fbeam / (2 * math.pi) * (pt[~ev].T @ (gl[~ev] * p0[~ev]))
-        rv = -(1.0 / (mu * sd)) * (lch @ (lch.T @ (sd * xs))) + xd / (mu * umu0)
+        rv = -(1.0 / (mu * sd)) * (lch @ (lch.T @ (sd * xs))) + (xd / (mu * umu0) if lam is None else xd * rl / mu)
         ttv = u.T @ np.linalg.solve(lch.T, np.linalg.solve(lch, (w / sd) * rv))   # V^T y2 = U^T L^-T y2
         ttv = ttv / den
         svec = (sd / w) * (u @ ttv)           # X tt, X = W^-1 D^1/2 L V = W^-1 D^1/2 U
         dd = linv(xd - mu * svec * rmu0)
-        att = math.exp(-tauc_top / umu0)
+        att = math.exp(-tauc_top / umu0) if lam is None else math.exp(-ch[0])
+        if e0_cap is not None:
+            att = e0_cap
         zp = 0.5 * (svec + dd) * att
         zm = 0.5 * (svec - dd) * att
     if not taup > 0.0:
@@ -156,8 +184,10 @@ def layer_ops(dtau, ssa, chi, nstr, umu0, fbeam, b_top, b_bot, tauc_top):
 
 def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
                  fisot=0.0, planck=False, temper=None, btemp=0.0, ttemp=0.0, temis=0.0,
-                 wvnmlo=0.0, wvnmhi=0.0):
-    """Layers top->bottom; returns (flup, fdn) at nlyr+1 levels top->bottom."""
+                 wvnmlo=0.0, wvnmhi=0.0, zd=None, radius=None):
+    """Layers top->bottom; returns (flup, fdn) at nlyr+1 levels top->bottom.  zd (bottom ->
+    top) and radius: the pseudo-spherical beam, its slant depths and secants evaluated in
+    double as the prologue kernel does (tests/spher_ref.py layer_secants)."""
     nn = nstr // 2
     mu, w = double_gauss(nn)
     nlyr = len(dtauc)
@@ -165,9 +195,24 @@ def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
     pk = [plkavg(wvnmlo, wvnmhi, tt) for tt in temper] if planck else [0.0] * (nlyr + 1)
     ops = []
     tauc = 0.0
+    chp = lamv = None
+    if zd is not None and beam:
+        from spher_ref import layer_secants
+        tp = []
+        for lc in range(nlyr):
+            s_ = ssalb[lc] if ssalb[lc] != 1.0 else 1.0 - DITHER
+            f_ = chis[lc][nstr - 1] if len(chis[lc]) >= nstr else 0.0
+            tp.append((1.0 - s_ * f_) * dtauc[lc])
+        chp, lamv = layer_secants(zd, radius, umu0, np.array(tp))
+
+    def direct(lev, tt):  # the direct beam's flux at a level
+        if not beam:
+            return 0.0
+        return umu0 * fbeam * (math.exp(-tt / umu0) if chp is None else math.exp(-chp[lev]))
     for lc in range(nlyr):
         o = layer_ops(dtauc[lc], ssalb[lc], chis[lc], nstr, umu0, fbeam if beam else 0.0,
-                      pk[lc], pk[lc + 1], tauc)
+                      pk[lc], pk[lc + 1], tauc, None if chp is None else lamv[lc],
+                      None if chp is None else (chp[lc], chp[lc + 1]))
         o["tauc_top"] = tauc
         tauc += o["taup"]
         ops.append(o)
@@ -186,7 +231,7 @@ def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
         sd = o["t"] @ u + o["sm"]
     e_surf = 0.0
     if beam:
-        e_surf += albedo * umu0 * fbeam * math.exp(-tauc / umu0) / math.pi
+        e_surf += albedo * direct(nlyr, tauc) / math.pi
     if planck:
         e_surf += (1 - albedo) * plkavg(wvnmlo, wvnmhi, btemp)
     wm = w * mu
@@ -194,12 +239,11 @@ def solve_column(dtauc, ssalb, chis, nstr, umu0=1.0, fbeam=0.0, albedo=0.0,
     ip = np.full(nn, xs)
     flup = np.zeros(nlyr + 1)
     fdn = np.zeros(nlyr + 1)
-    dirb = (lambda tt: umu0 * fbeam * math.exp(-tt / umu0)) if beam else (lambda tt: 0.0)
     flup[nlyr] = c @ ip
-    fdn[nlyr] = c @ (ra @ ip + sd) + dirb(tauc)
+    fdn[nlyr] = c @ (ra @ ip + sd) + direct(nlyr, tauc)
     for lc in range(nlyr - 1, -1, -1):
         zt, t_, rc, cs = store[lc]
         ip = zt @ ip + t_
         flup[lc] = c @ ip
-        fdn[lc] = rc @ ip + cs + dirb(ops[lc]["tauc_top"])
+        fdn[lc] = rc @ ip + cs + direct(lc, ops[lc]["tauc_top"])
     return flup, fdn

@@ -149,3 +149,60 @@ def test_model_shows_what_the_two_rules_replace(hard_fixture):
         kernel_model.RES_CLAMP, kernel_model.THIN_TAU = saved
     print(f"  clamp: {e_res:.3e}   dB/tau': {e_thin:.3e}")
     assert e_res > 1e3 * TOL and e_thin > 1e3 * TOL
+
+
+# --------------------------------------------------------------------------- #
+# the pseudo-spherical hard-regime fixture (tests/spher_hard_cases.py)
+# --------------------------------------------------------------------------- #
+@pytest.fixture(scope="module")
+def spher_fixture():
+    import spher_hard_cases
+    from helpers import GOLDEN
+    return spher_hard_cases.load(GOLDEN)
+
+
+def _spher_model_batch(b):
+    import spher_hard_cases
+    out = np.zeros((1, b["prop"].shape[1], b["nlyr"] + 1, 2))
+    for c in range(out.shape[1]):
+        (tau, ssa, pm, nstr), kw = spher_hard_cases.column_kwargs(b, c)
+        fu, fd = solve_column(tau, ssa, [list(r[1:]) for r in pm], nstr, **kw)
+        out[0, c, :, 0], out[0, c, :, 1] = fu[::-1], fd[::-1]
+    return out
+
+
+@pytest.mark.parametrize("nstr", [2, 4, 8, 16])
+@pytest.mark.parametrize("family", ["resonance", "low_sun", "depth", "conservative",
+                                    "thin_thermal", "phase"])
+def test_model_on_spher_hard_fixture(spher_fixture, family, nstr):
+    """Every pseudo-spherical fixture column with nstr <= 16 at TOL against the mp
+    reference."""
+    from helpers import TOL, rel_err
+    from oracle.disort_mp import flux_of_record
+    worst = 0.0
+    for b in spher_fixture[family, nstr]:
+        err = rel_err(_spher_model_batch(b), flux_of_record(b["ref"])).max(axis=(0, 2, 3))
+        print(f"  {family} n{nstr} {b['name']}: worst {err.max():.3e} (column {err.argmax()})")
+        worst = max(worst, err.max())
+    assert worst < TOL
+
+
+def test_model_shows_what_the_spher_move_replaces(spher_fixture):
+    """The clamp the SPHER layer kernels carried (one denominator at 1e-9 lambda^2) misses
+    TOL by orders of magnitude on the layer secant's resonance; the plain path's move
+    carried over without lambda's sign misses it where lambda < 0."""
+    import kernel_model
+    from helpers import TOL, rel_err
+    from oracle.disort_mp import flux_of_record
+    res = {b["name"]: b for b in spher_fixture["resonance", 8]}
+    saved = kernel_model.RES_CLAMP, kernel_model.KEEP_SIGN
+    try:
+        kernel_model.RES_CLAMP = 1.0e-9
+        e_clamp = rel_err(_spher_model_batch(res["scat"]), flux_of_record(res["scat"]["ref"])).max()
+        kernel_model.RES_CLAMP, kernel_model.KEEP_SIGN = None, False
+        e_sign = rel_err(_spher_model_batch(res["negative"]),
+                         flux_of_record(res["negative"]["ref"])).max()
+    finally:
+        kernel_model.RES_CLAMP, kernel_model.KEEP_SIGN = saved
+    print(f"  clamp: {e_clamp:.3e}   move without the sign: {e_sign:.3e}")
+    assert e_clamp > 1e3 * TOL and e_sign > TOL

@@ -3,7 +3,10 @@
 * against both double oracles on benign columns (where all three must agree to rounding),
 * against the published DISOTEST-1 fluxes and the closed forms of tests/test_oracle.py,
 * against itself at 50 and 90 digits on the inputs the double oracles fail on,
-* against the stored fixture tests/golden/flux_hard.npz (a stale file fails).
+* against the stored fixture tests/golden/flux_hard.npz (a stale file fails),
+* with zd / radius (the pseudo-spherical beam): against tests/spher_ref.py on benign
+  columns, against its own plane-parallel solve in the two limits, against an eigen-free
+  integration on a resonance, and against tests/golden/spher_hard.npz.
 """
 
 import math
@@ -13,6 +16,8 @@ import pytest
 from mpmath import mp
 
 import hard_cases
+import spher_hard_cases
+import spher_ref
 from flx_ref import flx_ref_column
 from helpers import GOLDEN, disotest, rel_err
 from oracle import disort_mp, disort_np
@@ -216,3 +221,158 @@ def test_resonance_umu0_sits_on_the_eigenvalue():
         assert abs(mp.mpf(float(b["bc"]["umu0"][0, 0])) * k - 1) < mp.mpf(2) ** -52
         d = [float(mp.mpf(float(u)) * k - 1) for u in b["bc"]["umu0"][0]]
     np.testing.assert_allclose(d[1:], hard_cases.DELTAS[1:], rtol=2e-3)
+
+
+# --------------------------------------------------------------------------- #
+# zd / radius: the pseudo-spherical beam
+# --------------------------------------------------------------------------- #
+@pytest.fixture(scope="module")
+def spher_fixture():
+    return spher_hard_cases.load(GOLDEN)
+
+
+@pytest.mark.parametrize("planck", [False, True], ids=["beam", "beam_planck"])
+@pytest.mark.parametrize("nstr", [2, 4, 8, 16])
+def test_spher_matches_spher_ref_on_benign_columns(nstr, planck):
+    """The batch of tests/test_gpu_spher.py (mu0 from 1 to 0.02, a layer of tau = 0, delta-M
+    active), per-column altitudes at nstr 8: the double restatement resolves these to
+    rounding.  The full record, 1e-12 in the project's metric."""
+    prop, bc, temf, zd = spher_ref.batch_inputs(nstr, "thin_bottom", planck, nstr == 8)
+    prop, bc = prop[:1], {k: v[:1] for k, v in bc.items()}
+    kw = dict(nstr=nstr, planck=planck, wave_lower=[spher_ref.WAVES[0][0]],
+              wave_upper=[spher_ref.WAVES[0][1]], zd=zd, radius=spher_ref.RADIUS)
+    flx, scale = disort_mp.flx_forward(prop, bc, temf, **kw)
+    flux, dflx, dscale = spher_ref.spher_forward(prop, bc, temf, **kw)
+    assert np.array_equal(disort_mp.disort_forward(prop, bc, temf, **kw),
+                          disort_mp.flux_of_record(flx))
+    e = rel_err(flux, disort_mp.flux_of_record(flx)).max()
+    print(f"  nstr {nstr} planck {planck}: fluxes {e:.2e}")
+    assert e < 1e-12
+    # the other entries are sums and differences of numbers no larger than the column's
+    # largest (rfldn at the top is rfldir - rfldir): 1e-12 of that, entry by entry
+    big = np.abs(flx).max(axis=(2, 3), keepdims=True)
+    assert (np.abs(dflx - flx) <= 1e-12 * big).all()
+    np.testing.assert_allclose(dscale, scale, rtol=1e-12)
+
+
+def _benign_column(nstr):
+    pm = np.array([[g ** l for l in range(nstr + 1)] for g in (0.5, 0.7, 0.6)])
+    return ([0.4, 1.0, 0.8], [0.6, 0.9, 0.7], pm, nstr), dict(
+        fbeam=1.3, albedo=0.3, planck=True, temper=[210.0, 230.0, 250.0, 270.0], btemp=275.0,
+        ttemp=140.0, temis=0.6, wvnmlo=500.0, wvnmhi=800.0)
+
+
+def test_spher_overhead_sun_is_plane_parallel():
+    """g = 1 identically at mu0 = 1, so ch' = tau', lambda = 1: the same numbers."""
+    args, kw = _benign_column(8)
+    a = disort_mp.disort_column(*args, umu0=1.0, zd=spher_hard_cases.ZD3, radius=3.39e6, **kw)
+    b = disort_mp.disort_column(*args, umu0=1.0, **kw)
+    assert np.abs(a["flx"] - b["flx"]).max() <= 1e-15 * np.abs(b["flx"]).max()
+
+
+def test_spher_large_radius_tends_to_plane_parallel():
+    """g - 1/mu0 = O(z / R): at R = 1e30 the difference is far below double rounding, at
+    R = 1e9 (z / R = 4.5e-5) it is that order."""
+    args, kw = _benign_column(8)
+    b = disort_mp.disort_column(*args, umu0=0.3, **kw)
+    far = disort_mp.disort_column(*args, umu0=0.3, zd=spher_hard_cases.ZD3, radius=1e30, **kw)
+    near = disort_mp.disort_column(*args, umu0=0.3, zd=spher_hard_cases.ZD3, radius=1e9, **kw)
+    scale = np.abs(b["flx"]).max()
+    assert np.abs(far["flx"] - b["flx"]).max() <= 1e-15 * scale
+    d = np.abs(near["flx"] - b["flx"]).max() / scale
+    assert 1e-7 < d < 1e-3, d
+
+
+@pytest.mark.parametrize("name,col", [("scat", 0), ("negative", 0), ("top", 0)])
+def test_spher_50_and_90_digits_agree_on_a_resonance(name, col):
+    _digits_agree([x for x in spher_hard_cases.batches("resonance", 8) if x["name"] == name][0],
+                  col)
+
+
+def test_spher_50_and_90_digits_agree_on_a_thin_layer():
+    """tau' 1e-12 under a thick layer (lambda about -5e12), mu0 = 1e-3."""
+    _digits_agree([x for x in spher_hard_cases.batches("low_sun", 8)
+                   if x["name"] == "thin_under_thick_planck"][0], 3)
+
+
+def _digits_agree(b, col):
+    args, kw = spher_hard_cases.column_kwargs(b, col)
+    a = disort_mp.disort_column(*args, dps=50, return_mp=True, **kw)["mp"]
+    c = disort_mp.disort_column(*args, dps=90, return_mp=True, **kw)["mp"]
+    with mp.workdps(90):
+        for k in range(8):
+            scale = max(abs(r[k]) for r in c)
+            if scale == 0:
+                assert all(r[k] == 0 for r in a)
+                continue
+            err = max(abs(x[k] - y[k]) for x, y in zip(a, c)) / scale
+            print(f"  component {k}: {mp.nstr(err, 3)}")
+            assert err < mp.mpf(10) ** -30
+
+
+def test_spher_resonance_against_the_propagator():
+    """nstr 2, the three-layer resonance column at delta = 0: spher_ref.propagator_column
+    integrates the 2N-stream equation by matrix exponentials, has no eigen-solution and is
+    regular where lambda = k_j -- an independent pin exactly where spher_ref.spher_column
+    is wrong by O(1).  (Not above nstr 2 on these depths: an initial-value integration.)"""
+    b = [x for x in spher_hard_cases.batches("resonance", 2) if x["name"] == "scat"][0]
+    c = int(np.flatnonzero(b["delta"] == 0.0)[0])
+    args, kw = spher_hard_cases.column_kwargs(b, c)
+    r = disort_mp.disort_column(*args, return_mp=True, **kw)
+    with mp.workdps(50):
+        assert abs(r["lam"][1] / r["kk"][1][0] - 1) < mp.mpf(10) ** -12
+    fu, fd, _, _ = spher_ref.propagator_column(*args, zd=kw["zd"], radius=kw["radius"],
+                                               umu0=kw["umu0"], fbeam=kw["fbeam"],
+                                               albedo=kw["albedo"])
+    e = rel_err(np.stack([fu, fd], -1)[None], np.stack([r["flup"], r["fdn"]], -1)[None]).max()
+    print(f"  propagator vs mp: {e:.2e}")
+    assert e < 1e-12
+    d = spher_ref.spher_column(*args, **kw)
+    e_ref = rel_err(np.stack([d["flup"], d["fdn"]], -1)[None],
+                    np.stack([r["flup"], r["fdn"]], -1)[None]).max()
+    print(f"  spher_ref.spher_column vs mp: {e_ref:.2e}")
+
+
+@pytest.mark.parametrize("family,nstr", [(f, n) for n in (2, 4, 8)
+                                         for f in spher_hard_cases.FAMILIES])
+def test_spher_fixture_is_current(spher_fixture, family, nstr):
+    """Inputs of every batch are what tests/spher_hard_cases.py builds, bitwise, and the
+    stored record of two columns per batch (one at nstr 2 and 4) is what the solver returns
+    now, to 1e-13."""
+    stored = {b["name"]: b for b in spher_fixture[family, nstr]}
+    built = spher_hard_cases.batches(family, nstr)
+    assert sorted(stored) == sorted(b["name"] for b in built)
+    for b in built:
+        s = stored[b["name"]]
+        assert np.array_equal(s["prop"], b["prop"]) and s["nmom"] == b["nmom"]
+        assert np.array_equal(s["zd"], b["zd"]) and s["radius"] == b["radius"]
+        assert sorted(s["bc"]) == sorted(b["bc"])
+        for k in b["bc"]:
+            assert np.array_equal(s["bc"][k], b["bc"][k]), k
+        assert (s["temf"] is None) == (b["temf"] is None)
+        if b["temf"] is not None:
+            assert np.array_equal(s["temf"], b["temf"])
+        if "delta" in b:
+            assert np.array_equal(s["delta"], b["delta"])
+            assert np.abs(s["delta_realised"] - b["delta"]).max() <= spher_hard_cases.DELTA_TOL
+        ncol = b["prop"].shape[1]
+        cols = sorted({0, ncol - 1}) if nstr == 8 else [ncol // 2]
+        ref, scale = spher_hard_cases.reference(b, cols)
+        assert rel_err(disort_mp.flux_of_record(s["ref"][:, cols]),
+                       disort_mp.flux_of_record(ref)).max() <= 1e-13
+        np.testing.assert_allclose(s["ref"][:, cols], ref, rtol=1e-13, atol=1e-13 * np.abs(ref).max())
+        np.testing.assert_allclose(s["scale"][:, cols], scale, rtol=1e-13, atol=0.0)
+
+
+def test_spher_fixture_covers_every_family_and_nstr(spher_fixture):
+    assert sorted(spher_fixture) == sorted((f, n) for f in spher_hard_cases.FAMILIES
+                                           for n in spher_hard_cases.NSTR)
+    shared = {f: False for f in spher_hard_cases.FAMILIES}
+    own = dict(shared)
+    for (family, _), bs in spher_fixture.items():
+        for b in bs:
+            assert np.all(np.isfinite(b["ref"])) and np.all(np.isfinite(b["scale"]))
+            assert b["nlyr"] <= 5 and b["prop"].shape[1] <= 24
+            shared[family] |= b["zd"].ndim == 1
+            own[family] |= b["zd"].ndim == 2
+    assert all(shared.values()) and all(own.values())  # both prologue addressings
