@@ -762,7 +762,7 @@ struct SolveCall {
   int prologue(long s0, int nsc, int buf, hipStream_t st) const {
     const hd::PlanckArgs pa = planck_args(cfg, in, at(hd::kRPlanck, buf), s0, nsc, cmaj);
     const hd::TaucArgs ta = tauc_args(cfg, in, at(hd::kRTauc, buf), s0, nsc, cmaj);
-    hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, st);
+    HD_HIP(ctx, hd::launch_prologue(planck ? &pa : nullptr, need_tauc ? &ta : nullptr, st));
     const hd::SphArgs sp = sph ? sph_args(nsc, buf) : hd::SphArgs{};
     if (sph) {
       hd::SpherProArgs xa{};
@@ -801,32 +801,22 @@ struct SolveCall {
     fa.nprop = cfg->nprop;
     fa.use_f = ta.use_f;
     fa.f_slot = ta.f_slot;
-    HD_HIP(ctx, sph ? hd::launch_flx_level_spher(fa, sp, st) : hd::launch_flx_level(fa, st));
+    HD_HIP(ctx, hd::launch_flx_level(fa, sph ? &sp : nullptr, st));
     return HD_OK;
   }
   // the path's kernels (pseudo-spherical: the SPHER instantiations of the plain ones)
   hipError_t layer(const hd::LayerArgs& la, int buf, hipStream_t st) const {
-    if (sph)
-      return reg ? hd::launch_layer_spher_nn(nn, la, sph_args(la.nsc, buf), st)
-                 : hd::launch_team_layer_spher_nn(nn, la, sph_args(la.nsc, buf), st);
-    return reg ? hd::launch_layer_nn(nn, la, st) : hd::launch_team_layer_nn(nn, la, st);
+    const hd::SphArgs sp = sph ? sph_args(la.nsc, buf) : hd::SphArgs{};
+    return hd::launch_layer(nn, la, sph ? &sp : nullptr, st);
   }
   hipError_t sweep(const hd::SweepArgs& sa, int buf, hipStream_t st) const {
-    if (sph) {
-      const hd::FlxArgs fx = flx_args(buf);
-      return reg ? hd::launch_sweep_spher_nn(nn, sa, sph_args(sa.nsc, buf), flx ? &fx : nullptr, st)
-                 : hd::launch_team_sweep_spher_nn(nn, sa, sph_args(sa.nsc, buf),
-                                                  flx ? &fx : nullptr, st);
-    }
-    if (reg)
-      return flx ? hd::launch_sweep_flx_nn(nn, sa, flx_args(buf), st)
-                 : hd::launch_sweep_nn(nn, sa, st);
-    return flx ? hd::launch_team_sweep_flx_nn(nn, sa, flx_args(buf), st)
-               : hd::launch_team_sweep_nn(nn, sa, st);
+    const hd::FlxArgs fx = flx_args(buf);
+    const hd::SphArgs sp = sph ? sph_args(sa.nsc, buf) : hd::SphArgs{};
+    return hd::launch_sweep(nn, sa, flx ? &fx : nullptr, sph ? &sp : nullptr, st);
   }
   hipError_t backsub(const hd::SweepArgs& sa, int buf, hipStream_t st, bool tail) const {
-    return flx ? hd::launch_backsub_flx_nn(nn, sa, flx_args(buf), st, tail)
-               : hd::launch_backsub_nn(nn, sa, st, tail);
+    const hd::FlxArgs fx = flx_args(buf);
+    return hd::launch_backsub(nn, sa, flx ? &fx : nullptr, st, tail);
   }
   int launch_failed(hipError_t e, const char* what = "launch") const {
     return fail(ctx, HD_EHIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
@@ -1444,7 +1434,7 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
     const int ns = (int)std::min(plan.chunk, nsolve - s0);
     const hd::TaucArgs ta = tauc_args(cfg, in, r_tauc, s0, ns);
     const hd::PlanckArgs pa = planck_args(cfg, in, r_planck, s0, ns);
-    hd::launch_prologue(planck ? &pa : nullptr, beam ? &ta : nullptr, stream);
+    HD_HIP(ctx, hd::launch_prologue(planck ? &pa : nullptr, beam ? &ta : nullptr, stream));
     hd::RadArgs a{};
     a.prop = in->prop;
     a.fbeam = in->fbeam;
@@ -1578,7 +1568,7 @@ int beer_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, dou
     const int nsc = (int)std::min(plan.chunk, nsolve - s0);
     if (planck) {
       const hd::PlanckArgs pa = planck_args(cfg, in, planck_q, s0, nsc);
-      hd::launch_prologue(&pa, nullptr, stream);
+      HD_HIP(ctx, hd::launch_prologue(&pa, nullptr, stream));
     }
     double* vals = out ? out + (size_t)s0 * m : local_q;  // the chunk's per-wave values
     hd::BeerArgs a{};

@@ -845,8 +845,12 @@ __device__ __forceinline__ int layer_body(const LayerArgs& A, long s, int sl, in
   return st;
 }
 
-template <int NN, bool NT>
-__global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
+// The frame of the two layer kernels: block numbering, prefetch target, the record
+// writer, layer_body and the status write.  SPHER (hd_solve_spher / hd_solve_flx_spher):
+// the pseudo-spherical beam, P the chunk's slant depths.  Shared, hd_layer_kernel<4> and
+// <5> take 66 SGPRs for 70, at the same occupancy and speed (profiles/lanewrap/README.md)
+template <int NN, bool NT, bool SPHER>
+__device__ __forceinline__ void layer_kernel_body(const LayerArgs& A, const SphArgs* P) {
   __shared__ double psi_lds[psi_doubles<NN>() * kLayerBlock];  // Psi^T staged per lane
   // block = 64 consecutive solves (one wave each) x kLayersPerBlock consecutive
   // layers: a wave's stores are coalesced (same layer, consecutive solves).
@@ -871,9 +875,11 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
   const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
   PairOutT<NT> out{reinterpret_cast<double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * A.nsc + sl,
                    (size_t)A.nsc, 0.0};
-#if HD_LAYER_PREFETCH
-  __shared__ float pf_sink[kLayerBlock];
   const double* pf = nullptr;
+  float* pf_sink = nullptr;
+#if HD_LAYER_PREFETCH
+  __shared__ float pf_lds[kLayerBlock];
+  pf_sink = pf_lds;
   if ((int)blockIdx.x + HD_LAYER_PREFETCH < nb) {
     int ts2, tl2;
     tile_of((int)blockIdx.x + HD_LAYER_PREFETCH, ts2, tl2);
@@ -885,70 +891,20 @@ __global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
       pf = A.prop + ((size_t)s2 * A.nlyr + (A.nlyr - 1 - lc2)) * A.nprop;
     }
   }
-  const int st =
-      layer_body<NN, NT>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink);
-#else
-  const int st =
-      layer_body<NN, NT>(A, s, sl, lc, psi_lds, lt, out);
 #endif
+  const int st = layer_body<NN, NT, SPHER>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink, P);
   if (st) {
     atomicOr(&A.status[s], st);
     if (st & 0x0F) atomicOr(A.anyerr, 1);
   }
 }
-// hd_solve_spher / hd_solve_flx_spher: hd_layer_kernel with the pseudo-spherical beam.  The
-// block numbering and prefetch are repeated here rather than shared through a function:
-// called through one, hd_layer_kernel<4> and <5> compiled to other SGPR counts
+template <int NN, bool NT>
+__global__ __launch_bounds__(kLayerBlock) void hd_layer_kernel(LayerArgs A) {
+  layer_kernel_body<NN, NT, false>(A, nullptr);
+}
 template <int NN, bool NT>
 __global__ __launch_bounds__(kLayerBlock) void hd_layer_spher_kernel(LayerArgs A, SphArgs P) {
-  __shared__ double psi_lds[psi_doubles<NN>() * kLayerBlock];  // Psi^T staged per lane
-  // block = 64 consecutive solves (one wave each) x kLayersPerBlock consecutive
-  // layers: a wave's stores are coalesced (same layer, consecutive solves).
-  // Neighbouring layers of a solve share 128-B lines of prop (18 doubles per
-  // record), so the blocks of one solve tile are numbered layer-fastest and
-  // dealt to the same XCD (blocks b and b + 8 share an XCD's L2): the second
-  // reader of a line finds it in L2 instead of HBM
-  const int lt = threadIdx.x;
-  const int ntl = (A.nlyr + kLayersPerBlock - 1) / kLayersPerBlock;
-  const int nb = (int)gridDim.x;
-  auto tile_of = [&](int b, int& ts, int& tl) {
-    const int x = b & 7, base = nb >> 3, extra = nb & 7;
-    const int logical = x * base + (x < extra ? x : extra) + (b >> 3);
-    ts = logical / ntl;
-    tl = logical - ts * ntl;
-  };
-  int ts, tl;
-  tile_of((int)blockIdx.x, ts, tl);
-  const int sl = ts * 64 + (lt & 63);
-  const int lc = tl * kLayersPerBlock + (lt >> 6);  // solver layer, 0 = top
-  if (sl >= A.nsc || lc >= A.nlyr) return;
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-  PairOutT<NT> out{reinterpret_cast<double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * A.nsc + sl,
-                   (size_t)A.nsc, 0.0};
-#if HD_LAYER_PREFETCH
-  __shared__ float pf_sink[kLayerBlock];
-  const double* pf = nullptr;
-  if ((int)blockIdx.x + HD_LAYER_PREFETCH < nb) {
-    int ts2, tl2;
-    tile_of((int)blockIdx.x + HD_LAYER_PREFETCH, ts2, tl2);
-    int sl2 = ts2 * 64 + (lt & 63);
-    const int lc2 = tl2 * kLayersPerBlock + (lt >> 6);
-    if (sl2 >= A.nsc) sl2 = A.nsc - 1;
-    if (lc2 < A.nlyr) {
-      const long s2 = solve_of(A.s0 + sl2, A.cmaj, A.nwave, A.ncol);
-      pf = A.prop + ((size_t)s2 * A.nlyr + (A.nlyr - 1 - lc2)) * A.nprop;
-    }
-  }
-  const int st =
-      layer_body<NN, NT, true>(A, s, sl, lc, psi_lds, lt, out, pf, pf_sink, &P);
-#else
-  const int st =
-      layer_body<NN, NT, true>(A, s, sl, lc, psi_lds, lt, out, nullptr, nullptr, &P);
-#endif
-  if (st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
+  layer_kernel_body<NN, NT, true>(A, &P);
 }
 // ============================================================================
 // K2: per-solve adding sweep + back-substitution
@@ -975,10 +931,9 @@ __device__ __forceinline__ void flx_emit(const FlxArgs& F, long s, long sl, size
 // The adding sweep of solve s (chunk lane sl): layer lc's record through
 // rec_at(lc), a callable returning a getter e -> RecL element e (loads from the
 // HBM record).  Stores the back-substitution records, the surface level and
-// x; returns the status bits.  The three wrappers below pass the same accessor:
-// stated once in here (or as one shared helper) it gave every sweep kernel
-// different instructions and registers, so it stays a parameter until that is
-// measured (profiles/retire/README.md).
+// x; returns the status bits.  sweep_kernel_body below states the accessor once
+// for the three kernels; sharing it moved two VGPRs of one instantiation and no
+// occupancy, scratch or speed (profiles/lanewrap/README.md).
 // FLX (hd_solve_flx): the records are RecBF -- each level also gets the mean-intensity
 // row rh and scalar ch -- and the surface level's eight components go to F->flx.
 // SPHER (pseudo-spherical beam): the direct beam at every level is exp(-ch') of
@@ -1309,60 +1264,41 @@ __device__ __forceinline__ int sweep_body(const SweepArgs& A, long sl, long s, R
   return st;
 }
 
+// The frame of the three one-lane sweep kernels: the lane's solve, the layer records'
+// accessor, sweep_body and the status write
+template <int NN, bool NT, bool FLX, bool SPHER>
+__device__ __forceinline__ void sweep_kernel_body(const SweepArgs& A, const FlxArgs* F,
+                                                  const SphArgs* P) {
+  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (sl >= A.nsc) return;
+  // hd_solve_flx never orders a chunk column-major (cmaj is 0 on its calls)
+  long s = A.s0 + sl;
+  if constexpr (!FLX || SPHER) s = solve_of(s, A.cmaj, A.nwave, A.ncol);
+  const size_t nsc = A.nsc;
+  auto rec_at = [&](int lc) {
+    const double2* lp =
+        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
+    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
+  };
+  const int st = sweep_body<NN, NT, FLX, SPHER>(A, sl, s, rec_at, F, P);
+  if (st) {
+    atomicOr(&A.status[s], st);
+    if (st & 0x0F) atomicOr(A.anyerr, 1);
+  }
+}
 template <int NN, bool NT>
 __global__ __launch_bounds__(64) void hd_sweep_kernel(SweepArgs A) {
-  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (sl >= A.nsc) return;
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-  const size_t nsc = A.nsc;
-  auto rec_at = [&](int lc) {
-    const double2* lp =
-        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
-    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
-  };
-  const int st = sweep_body<NN, NT>(A, sl, s, rec_at);
-  if (st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
+  sweep_kernel_body<NN, NT, false, false>(A, nullptr, nullptr);
 }
-
-// hd_solve_spher / hd_solve_flx_spher: the plain sweep with the pseudo-spherical beam
-template <int NN, bool NT, bool FLX>
-__global__ __launch_bounds__(64) void hd_sweep_spher_kernel(SweepArgs A, FlxArgs F, SphArgs P) {
-  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (sl >= A.nsc) return;
-  const long s = solve_of(A.s0 + sl, A.cmaj, A.nwave, A.ncol);
-  const size_t nsc = A.nsc;
-  auto rec_at = [&](int lc) {
-    const double2* lp =
-        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
-    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
-  };
-  const int st = sweep_body<NN, NT, FLX, true>(A, sl, s, rec_at, &F, &P);
-  if (st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
-}
-
-// hd_solve_flx's sweep: hd_sweep_kernel with the second functional (RecBF records)
+// hd_solve_flx's sweep: the second functional (RecBF records)
 template <int NN, bool NT>
 __global__ __launch_bounds__(64) void hd_sweep_flx_kernel(SweepArgs A, FlxArgs F) {
-  const long sl = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (sl >= A.nsc) return;
-  const long s = A.s0 + sl;
-  const size_t nsc = A.nsc;
-  auto rec_at = [&](int lc) {
-    const double2* lp =
-        reinterpret_cast<const double2*>(A.scr) + (size_t)lc * RecL<NN>::pairs * nsc + sl;
-    return [lp, nsc](int e) { return pair_get<NT>(lp, nsc, e); };
-  };
-  const int st = sweep_body<NN, NT, true>(A, sl, s, rec_at, &F);
-  if (st) {
-    atomicOr(&A.status[s], st);
-    if (st & 0x0F) atomicOr(A.anyerr, 1);
-  }
+  sweep_kernel_body<NN, NT, true, false>(A, &F, nullptr);
+}
+// hd_solve_spher / hd_solve_flx_spher: the pseudo-spherical beam
+template <int NN, bool NT, bool FLX>
+__global__ __launch_bounds__(64) void hd_sweep_spher_kernel(SweepArgs A, FlxArgs F, SphArgs P) {
+  sweep_kernel_body<NN, NT, FLX, true>(A, &F, &P);
 }
 
 template <int NN, bool PRE, bool NT, bool FLX = false>
@@ -1961,65 +1897,20 @@ hipError_t upload_quad_tables(const QuadHost* per_nn /* [kMaxNN], index nn-1 */)
   return hipMemcpyToSymbol(HIP_SYMBOL(c_quad), &t, sizeof(t), 0, hipMemcpyHostToDevice);
 }
 
-void launch_prologue(const PlanckArgs* pa, const TaucArgs* ta, hipStream_t stream) {
+hipError_t launch_prologue(const PlanckArgs* pa, const TaucArgs* ta, hipStream_t stream) {
+  hipError_t e = hipSuccess;
   if (ta) {
     hipLaunchKernelGGL(hd_tauc_kernel, dim3((unsigned)((ta->nsc + 255) / 256)), dim3(256), 0,
                        stream, *ta);
+    e = hipGetLastError();
   }
-  if (pa) {
+  if (pa && e == hipSuccess) {
     const long n0 = (long)pa->nsc * (pa->nlyr + 3);
     hipLaunchKernelGGL(hd_planck_kernel, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0,
                        stream, *pa);
+    e = hipGetLastError();
   }
-}
-
-template <int NN>
-static void launch_sweep(const SweepArgs& sa, hipStream_t stream) {
-  if constexpr (NN == 2 || NN == 4) {
-    if (sa.quad > 0 || (sa.quad < 0 && sa.nsc <= kQuadMaxSolves)) {  // NN-lane teams
-      hipLaunchKernelGGL(hd_sweep_quad_kernel<NN>, dim3((unsigned)((sa.nsc * NN + 63) / 64)),
-                         dim3(64), 0, stream, sa);
-      return;
-    }
-  }
-  if (sa.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_sweep_kernel<NN, true>), dim3((unsigned)((sa.nsc + 63) / 64)), dim3(64),
-                       0, stream, sa);
-  else
-    hipLaunchKernelGGL((hd_sweep_kernel<NN, false>), dim3((unsigned)((sa.nsc + 63) / 64)), dim3(64),
-                       0, stream, sa);
-}
-
-template <int NN>
-static void launch_backsub(const SweepArgs& sa, hipStream_t stream, bool tail) {
-  const dim3 gt((unsigned)((sa.nsc + 63) / 64)), gc((unsigned)((sa.nsc + 255) / 256));
-  const bool nt = sa.nsc >= kNtMinSolves;
-  if (tail && nt) hipLaunchKernelGGL((hd_backsub_tail_kernel<NN, true>), gt, dim3(64), 0, stream, sa);
-  else if (tail) hipLaunchKernelGGL((hd_backsub_tail_kernel<NN, false>), gt, dim3(64), 0, stream, sa);
-  else if (nt) hipLaunchKernelGGL((hd_backsub_kernel<NN, true>), gc, dim3(256), 0, stream, sa);
-  else hipLaunchKernelGGL((hd_backsub_kernel<NN, false>), gc, dim3(256), 0, stream, sa);
-}
-
-hipError_t launch_flx_level(const FlxLevelArgs& fa, hipStream_t stream) {
-  hipLaunchKernelGGL(hd_flx_level_kernel, dim3((unsigned)((fa.nsc + 255) / 256)), dim3(256), 0,
-                     stream, fa);
-  return hipGetLastError();
-}
-
-template <int NN>
-static void launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
-  const dim3 g((unsigned)((sa.nsc + 63) / 64));
-  if (sa.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_sweep_flx_kernel<NN, true>), g, dim3(64), 0, stream, sa, fx);
-  else
-    hipLaunchKernelGGL((hd_sweep_flx_kernel<NN, false>), g, dim3(64), 0, stream, sa, fx);
-}
-
-hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    launch_sweep_flx<NN>(sa, fx, stream);
-    return hipGetLastError();
-  });
+  return e;
 }
 
 hipError_t launch_spher_prologue(const SpherProArgs& pa, hipStream_t stream) {
@@ -2028,92 +1919,69 @@ hipError_t launch_spher_prologue(const SpherProArgs& pa, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_flx_level_spher(const FlxLevelArgs& fa, const SphArgs& sp, hipStream_t stream) {
-  hipLaunchKernelGGL(hd_flx_level_spher_kernel, dim3((unsigned)((fa.nsc + 255) / 256)), dim3(256),
-                     0, stream, fa, sp);
+hipError_t launch_flx_level(const FlxLevelArgs& fa, const SphArgs* sp, hipStream_t stream) {
+  const dim3 g((unsigned)((fa.nsc + 255) / 256));
+  if (sp) hipLaunchKernelGGL(hd_flx_level_spher_kernel, g, dim3(256), 0, stream, fa, *sp);
+  else hipLaunchKernelGGL(hd_flx_level_kernel, g, dim3(256), 0, stream, fa);
   return hipGetLastError();
 }
 
-template <int NN, bool FLX>
-static void launch_sweep_spher(const SweepArgs& sa, const FlxArgs& fx, const SphArgs& sp,
-                               hipStream_t stream) {
-  const dim3 g((unsigned)((sa.nsc + 63) / 64));
-  if (sa.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_sweep_spher_kernel<NN, true, FLX>), g, dim3(64), 0, stream, sa, fx, sp);
-  else
-    hipLaunchKernelGGL((hd_sweep_spher_kernel<NN, false, FLX>), g, dim3(64), 0, stream, sa, fx, sp);
-}
-
-hipError_t launch_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp, const FlxArgs* fx,
-                                 hipStream_t stream) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    if (fx) launch_sweep_spher<NN, true>(sa, *fx, sp, stream);
-    else launch_sweep_spher<NN, false>(sa, FlxArgs{}, sp, stream);
-    return hipGetLastError();
+hipError_t launch_layer(int nn, const LayerArgs& la, const SphArgs* sp, hipStream_t stream) {
+  if (nn > kMaxRegNN) return launch_team_layer(nn, la, sp, stream);
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NNc) {
+    constexpr int NN = decltype(NNc)::value;
+    const dim3 g((unsigned)(((la.nsc + 63) / 64) *
+                            ((la.nlyr + kLayersPerBlock - 1) / kLayersPerBlock)));
+    if (sp)
+      return launch_nt(la.nsc, g, dim3(kLayerBlock), stream,
+                       [](auto NT) { return hd_layer_spher_kernel<NN, NT>; }, la, *sp);
+    return launch_nt(la.nsc, g, dim3(kLayerBlock), stream,
+                     [](auto NT) { return hd_layer_kernel<NN, NT>; }, la);
   });
 }
 
-hipError_t launch_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp, hipStream_t stream) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    const unsigned nb1 = (unsigned)(((la.nsc + 63) / 64) *
-                                    ((la.nlyr + kLayersPerBlock - 1) / kLayersPerBlock));
-    if (la.nsc >= kNtMinSolves)
-      hipLaunchKernelGGL((hd_layer_spher_kernel<NN, true>), dim3(nb1), dim3(kLayerBlock), 0, stream,
-                         la, sp);
-    else
-      hipLaunchKernelGGL((hd_layer_spher_kernel<NN, false>), dim3(nb1), dim3(kLayerBlock), 0,
-                         stream, la, sp);
-    return hipGetLastError();
+hipError_t launch_sweep(int nn, const SweepArgs& sa, const FlxArgs* fx, const SphArgs* sp,
+                        hipStream_t stream) {
+  if (nn > kMaxRegNN) return launch_team_sweep(nn, sa, fx, sp, stream);
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NNc) {
+    constexpr int NN = decltype(NNc)::value;
+    const dim3 g((unsigned)((sa.nsc + 63) / 64)), b(64);
+    if (sp && fx)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_sweep_spher_kernel<NN, NT, true>; }, sa, *fx, *sp);
+    if (sp)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_sweep_spher_kernel<NN, NT, false>; }, sa,
+                       FlxArgs{}, *sp);
+    if (fx)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_sweep_flx_kernel<NN, NT>; }, sa, *fx);
+    if constexpr (NN == 2 || NN == 4) {
+      if (sa.quad > 0 || (sa.quad < 0 && sa.nsc <= kQuadMaxSolves)) {  // NN-lane teams
+        hipLaunchKernelGGL(hd_sweep_quad_kernel<NN>, dim3((unsigned)((sa.nsc * NN + 63) / 64)), b,
+                           0, stream, sa);
+        return hipGetLastError();
+      }
+    }
+    return launch_nt(sa.nsc, g, b, stream, [](auto NT) { return hd_sweep_kernel<NN, NT>; }, sa);
   });
 }
 
-template <int NN>
-static void launch_backsub_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream,
-                               bool tail) {
-  const dim3 gt((unsigned)((sa.nsc + 63) / 64)), gc((unsigned)((sa.nsc + 255) / 256));
-  const bool nt = sa.nsc >= kNtMinSolves;
-  if (tail && nt) hipLaunchKernelGGL((hd_backsub_flx_tail_kernel<NN, true>), gt, dim3(64), 0, stream, sa, fx);
-  else if (tail) hipLaunchKernelGGL((hd_backsub_flx_tail_kernel<NN, false>), gt, dim3(64), 0, stream, sa, fx);
-  else if (nt) hipLaunchKernelGGL((hd_backsub_flx_kernel<NN, true>), gc, dim3(256), 0, stream, sa, fx);
-  else hipLaunchKernelGGL((hd_backsub_flx_kernel<NN, false>), gc, dim3(256), 0, stream, sa, fx);
-}
-
-hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
-                                 hipStream_t stream, bool tail) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    launch_backsub_flx<NN>(sa, fx, stream, tail);
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bool tail) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    launch_backsub<NN>(sa, stream, tail);
-    return hipGetLastError();
-  });
-}
-
-template <int NN>
-static void launch_layer(const LayerArgs& la, hipStream_t stream) {
-  const unsigned nb1 = (unsigned)(((la.nsc + 63) / 64) *
-                                  ((la.nlyr + kLayersPerBlock - 1) / kLayersPerBlock));
-  if (la.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_layer_kernel<NN, true>), dim3(nb1), dim3(kLayerBlock), 0, stream, la);
-  else
-    hipLaunchKernelGGL((hd_layer_kernel<NN, false>), dim3(nb1), dim3(kLayerBlock), 0, stream, la);
-}
-
-hipError_t launch_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    launch_layer<NN>(la, stream);
-    return hipGetLastError();
-  });
-}
-
-hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {
-  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    launch_sweep<NN>(sa, stream);
-    return hipGetLastError();
+hipError_t launch_backsub(int nn, const SweepArgs& sa, const FlxArgs* fx, hipStream_t stream,
+                          bool tail) {
+  return dispatch_nn<1, kMaxRegNN>(nn, [&](auto NNc) {
+    constexpr int NN = decltype(NNc)::value;
+    const dim3 g((unsigned)((sa.nsc + (tail ? 63 : 255)) / (tail ? 64 : 256))), b(tail ? 64 : 256);
+    if (fx && tail)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_backsub_flx_tail_kernel<NN, NT>; }, sa, *fx);
+    if (fx)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_backsub_flx_kernel<NN, NT>; }, sa, *fx);
+    if (tail)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_backsub_tail_kernel<NN, NT>; }, sa);
+    return launch_nt(sa.nsc, g, b, stream, [](auto NT) { return hd_backsub_kernel<NN, NT>; }, sa);
   });
 }
 

@@ -358,36 +358,35 @@ inline hipError_t dispatch_nn(int nn, F&& f) {
 // copy the quadrature tables (index nn-1) into the current device's constant memory
 hipError_t upload_quad_tables(const QuadHost* per_nn);       // nn 1..kMaxRegNN
 hipError_t upload_quad_tables_team(const QuadHost* per_nn);  // nn kMaxRegNN+1..kMaxNN
+// The launchers' choice between a kernel's two store forms: mk(std::bool_constant<NT>)
+// is the kernel, NT (nontemporal record stores) for a chunk of at least kNtMinSolves
+template <class MK, class... Args>
+inline hipError_t launch_nt(int nsc, dim3 grid, dim3 block, hipStream_t stream, MK&& mk,
+                            const Args&... args) {
+  if (nsc >= kNtMinSolves)
+    hipLaunchKernelGGL(mk(std::true_type{}), grid, block, 0, stream, args...);
+  else
+    hipLaunchKernelGGL(mk(std::false_type{}), grid, block, 0, stream, args...);
+  return hipGetLastError();
+}
+
 // cumulative scaled depth (beam) and level Planck radiances (planck) of a chunk
-void launch_prologue(const PlanckArgs* pa, const TaucArgs* ta, hipStream_t stream);
-// back-substitution of a register-path chunk (reads sa.bsub / sa.xsurf)
-hipError_t launch_backsub_nn(int nn, const SweepArgs& sa, hipStream_t stream, bool tail);
-// register path, separately: the layer kernel and the adding sweep of one chunk
-hipError_t launch_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
-hipError_t launch_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
-// hd_solve_flx: the per-level prologue, the plain one-lane sweep and the back-substitution
-// with the second functional (register path), the one-wave team sweep with it (team path)
-hipError_t launch_flx_level(const FlxLevelArgs& fa, hipStream_t stream);
-hipError_t launch_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream);
-hipError_t launch_backsub_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
-                                 hipStream_t stream, bool tail);
-hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
-                                    hipStream_t stream);
-// pseudo-spherical solves (hd_solve_spher, hd_solve_flx_spher): the chunk's prologue, then
-// the SPHER instantiations of the plain kernels of either path (fx null: the two fluxes;
-// the register path's back-substitutions are the plane-parallel ones)
+hipError_t launch_prologue(const PlanckArgs* pa, const TaucArgs* ta, hipStream_t stream);
+// pseudo-spherical solves: the chunk's slant depths and secants
 hipError_t launch_spher_prologue(const SpherProArgs& pa, hipStream_t stream);
-hipError_t launch_flx_level_spher(const FlxLevelArgs& fa, const SphArgs& sp, hipStream_t stream);
-hipError_t launch_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp, hipStream_t stream);
-hipError_t launch_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp, const FlxArgs* fx,
-                                 hipStream_t stream);
-hipError_t launch_team_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp,
-                                      hipStream_t stream);
-hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp,
-                                      const FlxArgs* fx, hipStream_t stream);
-// team path: the layer kernel and the sweep of one chunk (hd_team_mfma.hip)
-hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream);
-hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream);
+// The flux path's stages of one chunk.  sp: the pseudo-spherical beam (hd_solve_spher,
+// hd_solve_flx_spher), fx: the second functional (hd_solve_flx); either may be null.
+// nn <= kMaxRegNN runs the one-lane kernels, larger nn the team kernels of
+// hd_team_mfma.hip (launch_team_*, which have no separate back-substitution)
+hipError_t launch_layer(int nn, const LayerArgs& la, const SphArgs* sp, hipStream_t stream);
+hipError_t launch_sweep(int nn, const SweepArgs& sa, const FlxArgs* fx, const SphArgs* sp,
+                        hipStream_t stream);
+hipError_t launch_backsub(int nn, const SweepArgs& sa, const FlxArgs* fx, hipStream_t stream,
+                          bool tail);
+hipError_t launch_flx_level(const FlxLevelArgs& fa, const SphArgs* sp, hipStream_t stream);
+hipError_t launch_team_layer(int nn, const LayerArgs& la, const SphArgs* sp, hipStream_t stream);
+hipError_t launch_team_sweep(int nn, const SweepArgs& sa, const FlxArgs* fx, const SphArgs* sp,
+                             hipStream_t stream);
 // the chunk epilogue of hd_solve_band (after the chunk's back-substitution)
 hipError_t launch_band_reduce(const BandArgs& ba, hipStream_t stream);
 // A/B switches between the kernels of the library (HD_JACOBI_WARM, HD_SWEEP_QUAD,

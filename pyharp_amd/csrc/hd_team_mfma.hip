@@ -1544,77 +1544,38 @@ hipError_t upload_quad_tables_team(const QuadHost* per_nn /* [kMaxNN], index nn-
 
 // the layer kernel and the sweep of one chunk (hd_solve launches them on one stream, or
 // chunk k+1's layer kernel on one stream beside chunk k's sweep on another)
-template <int NN>
-static hipError_t launch_layer(const LayerArgs& la, hipStream_t stream) {
-  static_assert(ne1t<NN>() % 2 == 0 && ne2t<NN>() % 2 == 0, "16-byte aligned records");
-  const unsigned nb1 = (unsigned)(((la.nsc + 3) / 4) * (long)la.nlyr);
-  if (la.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_team_mfma_layer_kernel<NN, true>), dim3(nb1), dim3(64), 0, stream, la);
-  else
-    hipLaunchKernelGGL((hd_team_mfma_layer_kernel<NN, false>), dim3(nb1), dim3(64), 0, stream, la);
-  return hipGetLastError();
-}
-
-template <int NN>
-static hipError_t launch_sweep(const SweepArgs& sa, hipStream_t stream) {
-  const dim3 gl((unsigned)((sa.nsc + 3) / 4));
-  if (sa.nsc >= kNtMinSolves)
-    hipLaunchKernelGGL((hd_team_mfma_sweep_lean_kernel<NN, true>), gl, dim3(64), 0, stream, sa);
-  else
-    hipLaunchKernelGGL((hd_team_mfma_sweep_lean_kernel<NN, false>), gl, dim3(64), 0, stream, sa);
-  return hipGetLastError();
-}
-
-hipError_t launch_team_sweep_nn(int nn, const SweepArgs& sa, hipStream_t stream) {
-  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
-      nn, [&](auto NN) { return launch_sweep<NN>(sa, stream); });
-}
-
-template <int NN>
-static hipError_t launch_sweep_flx(const SweepArgs& sa, const FlxArgs& fx, hipStream_t stream) {
-  static_assert(ne2tf<NN>() % 2 == 0, "16-byte aligned records");
-  hipLaunchKernelGGL(hd_team_mfma_sweep_flx_kernel<NN>, dim3((unsigned)((sa.nsc + 3) / 4)),
-                     dim3(64), 0, stream, sa, fx);
-  return hipGetLastError();
-}
-
-hipError_t launch_team_sweep_flx_nn(int nn, const SweepArgs& sa, const FlxArgs& fx,
-                                    hipStream_t stream) {
-  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
-      nn, [&](auto NN) { return launch_sweep_flx<NN>(sa, fx, stream); });
-}
-
-hipError_t launch_team_layer_spher_nn(int nn, const LayerArgs& la, const SphArgs& sp,
-                                      hipStream_t stream) {
-  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NN) {
-    const unsigned nb1 = (unsigned)(((la.nsc + 3) / 4) * (long)la.nlyr);
-    if (la.nsc >= kNtMinSolves)
-      hipLaunchKernelGGL((hd_team_mfma_layer_spher_kernel<NN, true>), dim3(nb1), dim3(64), 0,
-                         stream, la, sp);
-    else
-      hipLaunchKernelGGL((hd_team_mfma_layer_spher_kernel<NN, false>), dim3(nb1), dim3(64), 0,
-                         stream, la, sp);
-    return hipGetLastError();
+hipError_t launch_team_layer(int nn, const LayerArgs& la, const SphArgs* sp, hipStream_t stream) {
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NNc) {
+    constexpr int NN = decltype(NNc)::value;
+    static_assert(ne1t<NN>() % 2 == 0 && ne2t<NN>() % 2 == 0, "16-byte aligned records");
+    const dim3 g((unsigned)(((la.nsc + 3) / 4) * (long)la.nlyr)), b(64);
+    if (sp)
+      return launch_nt(la.nsc, g, b, stream,
+                       [](auto NT) { return hd_team_mfma_layer_spher_kernel<NN, NT>; }, la, *sp);
+    return launch_nt(la.nsc, g, b, stream,
+                     [](auto NT) { return hd_team_mfma_layer_kernel<NN, NT>; }, la);
   });
 }
 
-hipError_t launch_team_sweep_spher_nn(int nn, const SweepArgs& sa, const SphArgs& sp,
-                                      const FlxArgs* fx, hipStream_t stream) {
-  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NN) {
-    const dim3 g((unsigned)((sa.nsc + 3) / 4));
-    if (fx)
-      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, true>), g, dim3(64), 0, stream, sa,
-                         *fx, sp);
+// fx or sp: the one-wave sweeps (FluxSweepPath); neither: the lean sweep
+hipError_t launch_team_sweep(int nn, const SweepArgs& sa, const FlxArgs* fx, const SphArgs* sp,
+                             hipStream_t stream) {
+  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(nn, [&](auto NNc) {
+    constexpr int NN = decltype(NNc)::value;
+    static_assert(ne2tf<NN>() % 2 == 0, "16-byte aligned records");
+    const dim3 g((unsigned)((sa.nsc + 3) / 4)), b(64);
+    if (!fx && !sp)
+      return launch_nt(sa.nsc, g, b, stream,
+                       [](auto NT) { return hd_team_mfma_sweep_lean_kernel<NN, NT>; }, sa);
+    if (sp && fx)
+      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, true>), g, b, 0, stream, sa, *fx, *sp);
+    else if (sp)
+      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, false>), g, b, 0, stream, sa,
+                         FlxArgs{}, *sp);
     else
-      hipLaunchKernelGGL((hd_team_mfma_sweep_spher_kernel<NN, false>), g, dim3(64), 0, stream, sa,
-                         FlxArgs{}, sp);
+      hipLaunchKernelGGL(hd_team_mfma_sweep_flx_kernel<NN>, g, b, 0, stream, sa, *fx);
     return hipGetLastError();
   });
-}
-
-hipError_t launch_team_layer_nn(int nn, const LayerArgs& la, hipStream_t stream) {
-  return dispatch_nn<kMaxRegNN + 1, kMaxNN>(
-      nn, [&](auto NN) { return launch_layer<NN>(la, stream); });
 }
 
 

@@ -111,7 +111,23 @@ def dump(out_dir):
         st = torch.zeros(4099, dtype=torch.int32, device=dev)
         save(f"forward_nt_n{nstr}", d.forward(t(prop), tb(bc), t(temf), status=st))
         save(f"forward_nt_n{nstr}_status", st)
-    del prop, bc, temf
+    # the same on the one-lane path (nstr 6 and 16: at 4 and 8 a chunk this small runs the quad
+    # sweep): the nontemporal layer kernel, sweep and back-substitution, plain, with the
+    # pseudo-spherical beam, and with it and the second functional
+    for nstr in (6, 16):
+        rng = np.random.default_rng(4099 + nstr)
+        prop, bc, temf = _inputs(rng, 1, 4099, 2, nstr, 1, 1)
+        a = (t(prop), tb(bc), t(temf))
+        zd = t(np.linspace(0.0, 20.0e3, 3))
+        d = disort(nstr, 2, 1, 4099, 1)
+        ds = disort(nstr, 2, 1, 4099, 1, flags="lamber,quiet,onlyfl,spher", radius=3.39e6)
+        for name, call in (("forward_nt", lambda st: d.forward(*a, status=st)),
+                           ("spher_nt", lambda st: ds.forward(*a, zd=zd, status=st)),
+                           ("flx_spher_nt", lambda st: ds.forward_flx(*a, zd=zd, status=st))):
+            st = torch.zeros(4099, dtype=torch.int32, device=dev)
+            save(f"{name}_n{nstr}", call(st))
+            save(f"{name}_n{nstr}_status", st)
+    del prop, bc, temf, a
 
     # ---- the smallest call on hd_solve_band's row-major route
     rng = np.random.default_rng(77)

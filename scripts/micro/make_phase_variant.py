@@ -36,8 +36,8 @@ tick("  // thermal: cvec = dB + 2 (dB/tau') h,  h = W^-1 D^1/2 L^-T L^-1 D^1/2 m
 tick("  // ---- eigenpairs (c_soleig)", 3)
 tick("  // L is not needed again until the beam solution: park it", 4)
 tick("  if (!jacobi_os<NN>(v, A.max_sweeps)) st |= kStEigen;\n", 5)
-tick("  jacobi_os_polish<NN>(v, beam && near_resonance<NN>(v, rmu0 * rmu0, kResPolish));\n", 6,
-     after=True)
+tick("  if (jacobi_os_polish<NN>(v, beam && near_resonance<NN>(k2, rmu0 * rmu0, kResPolish)))\n"
+     "    column_norms2<NN>(v, k2);\n", 6, after=True)
 tick("  // beam, the part that needs only B and k", 7)
 tick("  // ---- beam particular solution Z+/- (c_upbeam)", 8)
 tick("  // ---- layer operators in the flux-weighted basis ----\n", 9)
@@ -46,14 +46,7 @@ tick("  // Omega = U Delta^1/2 = L B K^-1 Delta^1/2, in place", 11)
 tick("  using RL = RecL<NN>;\n", 12)
 tick("  double ap_[NN][NN], qvec[NN];\n", 13)
 tick("  // ---- store: R~ = A+ - A-", 14)
-leg_end = """  }
-#pragma unroll
-  for (int i = 0; i < NN; ++i)
-#pragma unroll
-    for (int j = i; j < NN; ++j) {
-      const double diag = (i == j) ? Qc.rmu[i] : 0.0;"""
-assert body.count(leg_end) == 1
-body = body.replace(leg_end, leg_end.replace("  }\n", "  }\n  HD_TICK(18);\n", 1))
+# phase 18 (the scaling pass after the Legendre loop) is gone: phase 1 ends at the loop's end
 body += """  HD_TICK(15);
   if ((threadIdx.x & 63) == 0)
     for (int k_ = 1; k_ < 20; ++k_) atomicAdd(&d_phase[k_], (unsigned long long)ph_[k_]);

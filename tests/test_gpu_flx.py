@@ -34,12 +34,14 @@ NAMES = ("rfldir", "rfldn", "flup", "dfdt", "uavg", "uavgdn", "uavgup", "uavgso"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _disort(nstr, nlyr, nwave, ncol, planck=False, wl=None, wu=None, extra=""):
+def _disort(nstr, nlyr, nwave, ncol, planck=False, wl=None, wu=None, extra="", radius=None):
     from pyharp_amd import Disort, DisortOptions
     op = DisortOptions().flags("lamber,quiet,onlyfl" + (",planck" if planck else "") + extra)
     op.nwave(nwave).ncol(ncol)
     if planck:
         op.wave_lower(list(map(float, wl))).wave_upper(list(map(float, wu)))
+    if radius is not None:
+        op.radius(radius)
     op.ds().nlyr = nlyr
     op.ds().nstr = nstr
     op.ds().nmom = nstr
@@ -205,6 +207,47 @@ def test_team_large_chunk_bitwise_with_small_chunks(nstr):
             ctx.set_chunk(0)
     (f, st), (f2, st2) = out
     assert np.all(np.isfinite(f)) and np.all(f[..., 0] > 0.0)
+    assert np.array_equal(f, f2)
+    assert np.array_equal(st, st2)
+
+
+@pytest.mark.parametrize("call", ["forward", "forward_spher", "forward_flx_spher"])
+@pytest.mark.parametrize("nstr", [6, 16])
+def test_reg_large_chunk_bitwise_with_small_chunks(nstr, call):
+    """The same on the one-lane path (nstr 6 and 16: at 4 and 8 a chunk this small runs the
+    quad sweep): one chunk of 4 099 solves takes the nontemporal instantiations of
+    hd_layer_kernel / hd_sweep_kernel (forward), of hd_layer_spher_kernel /
+    hd_sweep_spher_kernel (forward with zd) and of the latter's FLX form with the flx
+    back-substitution (forward_flx with zd); chunks of 1 024 take the plain ones."""
+    from pyharp_amd import _lib
+    from pyharp_amd.disort import _context
+    nwave, ncol, nlyr = 1, 4099, 2
+    assert _lib.chunk_solves(nstr, nlyr, nwave * ncol, planck=True) == nwave * ncol
+    rng = np.random.default_rng(4099 + nstr)
+    prop, bc = _hg_batch(rng, nwave, ncol, nlyr, nstr)
+    bc.update(btemp=np.full((nwave, ncol), 290.0), ttemp=np.full((nwave, ncol), 160.0),
+              temis=rng.uniform(0.1, 0.9, (nwave, ncol)))
+    temf = np.linspace(285.0, 190.0, nlyr + 1)[None, :] + rng.uniform(-5, 5, (ncol, nlyr + 1))
+    spher = call != "forward"
+    d = _disort(nstr, nlyr, nwave, ncol, planck=True, wl=[200.0], wu=[400.0],
+                extra=",spher" if spher else "", radius=3.39e6 if spher else None)
+    p, b, t = _dev(prop, bc, temf)
+    kw = {}
+    if spher:
+        kw["zd"] = torch.as_tensor(np.linspace(0.0, 20.0e3, nlyr + 1), dtype=torch.float64,
+                                   device=p.device)
+    fwd = d.forward_flx if call == "forward_flx_spher" else d.forward
+    ctx = _context(0)
+    out = []
+    for chunk in (0, 1024):
+        st = torch.zeros(nwave * ncol, dtype=torch.int32, device=p.device)
+        ctx.set_chunk(chunk)
+        try:
+            out.append((fwd(p, b, t, status=st, **kw).cpu().numpy(), st.cpu().numpy()))
+        finally:
+            ctx.set_chunk(0)
+    (f, st), (f2, st2) = out
+    assert np.all(np.isfinite(f)) and np.all(f[..., IFLUP if f.shape[-1] == NFLX else 0] > 0.0)
     assert np.array_equal(f, f2)
     assert np.array_equal(st, st2)
 
