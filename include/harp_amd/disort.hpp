@@ -396,9 +396,16 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   //! grid solve + bilinear interpolation of the legacy CalBandRadiance
   //! (rt_solver_disort.cpp_:210-286).  Needs a module without onlyfl; depths are
   //! user_tau with usrtau, else the layer boundaries; user_mu / user_phi are not used.
+  //! zd given: the pseudo-spherical beam (hd_solve_rays_spher) with options.radius() as the
+  //! planet radius -- the level altitudes above it, bottom -> top, float64 (nlyr+1) shared
+  //! by all columns or (ncol, nlyr+1), staged to the solve device like umu.  nstr <= 16.
+  //! The 'spher' flag is not needed (and cannot be set on a module with radiances);
+  //! without zd the call is the plane-parallel one.
   torch::Tensor forward_rays(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
-                             torch::Tensor temf, torch::Tensor umu, torch::Tensor phi) {
-    return solve_rays("Disort.forward_rays", prop, bc, temf, umu, phi, torch::Tensor(), nullptr);
+                             torch::Tensor temf, torch::Tensor umu, torch::Tensor phi,
+                             torch::Tensor zd = torch::Tensor()) {
+    return solve_rays("Disort.forward_rays", prop, bc, temf, umu, phi, torch::Tensor(), nullptr,
+                      zd);
   }
 
   //! band radiance (ncol, ntau, nray) = sum_w weights[w] rad[w] with the sum fused into
@@ -407,9 +414,10 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   //! set to a (nwave, ncol, ntau, nray) tensor on the input's device).
   torch::Tensor forward_rays_band(torch::Tensor prop, std::map<std::string, torch::Tensor>* bc,
                                   torch::Tensor temf, torch::Tensor umu, torch::Tensor phi,
-                                  torch::Tensor weights, torch::Tensor* rad = nullptr) {
+                                  torch::Tensor weights, torch::Tensor* rad = nullptr,
+                                  torch::Tensor zd = torch::Tensor()) {
     TORCH_CHECK(weights.defined(), "Disort.forward_rays_band: weights are required");
-    return solve_rays("Disort.forward_rays_band", prop, bc, temf, umu, phi, weights, rad);
+    return solve_rays("Disort.forward_rays_band", prop, bc, temf, umu, phi, weights, rad, zd);
   }
 
  protected:
@@ -469,9 +477,19 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
   torch::Tensor solve_rays(const char* who, torch::Tensor prop,
                            std::map<std::string, torch::Tensor>* bc, torch::Tensor temf,
                            torch::Tensor umu, torch::Tensor phi, torch::Tensor weights,
-                           torch::Tensor* rad_out) {
+                           torch::Tensor* rad_out, torch::Tensor zd) {
     TORCH_CHECK(!onlyfl_, who, ": radiances are off (clear the 'onlyfl' flag)");
     TORCH_CHECK(prop.dim() == 4, who, ": prop must be (nwave, ncol, nlyr, nprop)");
+    if (zd.defined()) {  // the pseudo-spherical beam: checked before the device is touched
+      TORCH_CHECK(std::isfinite(options.radius()) && options.radius() > 0.0, who,
+                  ": zd given: pseudo-spherical geometry needs DisortOptions.radius (finite, > 0)");
+      TORCH_CHECK(zd.scalar_type() == torch::kFloat64, who, ": zd must be a float64 tensor");
+      TORCH_CHECK((zd.dim() == 1 || (zd.dim() == 2 && zd.size(0) == prop.size(1))) &&
+                      zd.size(-1) == options.ds().nlyr + 1,
+                  who, ": zd must be (nlyr+1) or (ncol, nlyr+1)");
+      TORCH_CHECK(options.ds().nstr <= 16, who,
+                  ": zd given: pseudo-spherical ray radiances support nstr <= 16");
+    }
     TORCH_CHECK(umu.defined() && phi.defined() && umu.scalar_type() == torch::kFloat64 &&
                     phi.scalar_type() == torch::kFloat64,
                 who, ": umu and phi must be float64 tensors");
@@ -496,9 +514,17 @@ class DisortImpl : public torch::nn::Cloneable<DisortImpl> {
                  band ? w.data_ptr<double>() : nullptr,
                  band ? brad.data_ptr<double>() : nullptr};
     auto stream = at::hip::getCurrentHIPStream(x.dev.index()).stream();
-    const int rc = hd_solve_rays(context(x.dev.index()), &x.cfg, &x.in, &rays, nullptr,
-                                 rad.defined() ? rad.data_ptr<double>() : nullptr, nullptr,
-                                 reinterpret_cast<void*>(stream));
+    double* radp = rad.defined() ? rad.data_ptr<double>() : nullptr;
+    int rc;
+    if (zd.defined()) {
+      auto z = zd.to(x.f64).contiguous();
+      hd_sphere sph{options.radius(), z.data_ptr<double>(), zd.dim() == 2 ? 1 : 0};
+      rc = hd_solve_rays_spher(context(x.dev.index()), &x.cfg, &x.in, &sph, &rays, nullptr, radp,
+                               nullptr, reinterpret_cast<void*>(stream));
+    } else {
+      rc = hd_solve_rays(context(x.dev.index()), &x.cfg, &x.in, &rays, nullptr, radp, nullptr,
+                         reinterpret_cast<void*>(stream));
+    }
     TORCH_CHECK(rc == HD_OK, "DisortWrapper::Run failed: ", hd_last_error(context(x.dev.index())));
     if (rad_out) *rad_out = x.in_dev.is_cuda() ? rad : rad.to(x.in_dev);
     auto res = band ? brad : rad;

@@ -63,7 +63,8 @@ extern "C" {
  * hd_solve_flx -- cdisort's rfldir, rfldn, flup, dfdt, uavg, uavgdn, uavgup, uavgso
  * at the layer boundaries -- with onlyfl and without usrtau); spher (pseudo-spherical
  * beam geometry: hd_solve_spher / hd_solve_flx_spher) is honoured with onlyfl and
- * without usrtau once a planet radius is configured, and refused otherwise; ibcnd is
+ * without usrtau once a planet radius is configured, and refused otherwise (the ray
+ * radiances take the geometry per call instead: hd_solve_rays_spher); ibcnd is
  * refused as harp's driver refuses it (src/rtsolver/rt_solver_disort.cpp_:67-68), and
  * so are general_source, output_uum and the new intensity correction (not
  * implemented); unknown names are refused. */
@@ -93,7 +94,9 @@ extern "C" {
                                     calls do the same with each layer's own beam secant,
                                     of either sign, in place of 1/umu0.  The radiance
                                     paths clamp the one denominator instead (within 5e-10)
-                                    and lose that mode's beam source there */
+                                    and lose that mode's beam source there; under
+                                    hd_solve_rays_spher the clamp is keyed on the layer's
+                                    secant, lambda^2 against k^2, for either sign of lambda */
 #define HD_STATUS_PIVOT 0x20     /* warning: tiny pivot in the boundary sweep      */
 #define HD_STATUS_ERROR_MASK 0x0F
 
@@ -391,6 +394,31 @@ typedef struct hd_rays {
 
 int hd_solve_rays(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
                   const hd_rays *rays, double *flux, double *rad, int *status, void *stream);
+
+/*
+ * hd_solve_rays with the pseudo-spherical beam of hd_solve_spher (DESIGN.md sections 3e
+ * and 3b): sph as documented there (radius, DEVICE zd, per_column).  In every azimuthal
+ * mode the beam of layer j is one exponential in tau' with the layer's secant lambda_j
+ * and the amplitude F0 exp(-ch'_top(j)) at the layer top; the factor 2 - delta_m0 and
+ * Y_l^m(mu0), cos(Theta) at the true mu0 are unchanged.  The surface is lit by
+ * mu0 F0 exp(-ch'_0), flux holds the direct term mu0 F0 exp(-ch'(utau)) on the scaled
+ * depth as hd_solve_rays (at the layer boundaries, ntau = 0, flux is hd_solve_spher's own
+ * output, bit for bit: that solve runs first, and status then carries its bits too), and
+ * with corint = 1 the TMS step integrates that beam, while the IMS step -- a
+ * plane-parallel slab average with no spherical form in cdisort -- takes for mu0 the mean
+ * cosine of the slab above the user depth, utau / ch(utau), ch the unscaled slant depth
+ * (linear in tau inside the user's layer): this library's own definition, equal to mu0 as
+ * R -> infinity.  Without sph (hd_solve_rays) nothing changes.
+ * nstr 2..16 only: nstr > 16 is HD_EINVAL, as are a radius that is not finite or <= 0 and
+ * a NULL zd.  A column with a bad zd (not finite, not strictly increasing, R + z_0 <= 0)
+ * sets HD_STATUS_BAD_INPUT on its solves, which run with the beam off.  Outputs, band
+ * sum, status, ordering on the context and the no-capture rule as hd_solve_rays.  No
+ * accuracy is claimed where a layer's lambda_j^2 meets one of its k^2
+ * (HD_STATUS_RESONANCE: that one denominator is clamped).
+ */
+int hd_solve_rays_spher(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                        const hd_sphere *sph, const hd_rays *rays, double *flux, double *rad,
+                        int *status, void *stream);
 
 /* host helper: the double-Gauss quadrature the kernels use (nstr/2 nodes on (0,1)) */
 int hd_quadrature(int nstr, double *mu, double *w);

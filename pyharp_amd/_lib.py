@@ -28,7 +28,7 @@ EXPORTED = ("hd_version", "hd_last_error", "hd_context_create", "hd_context_dest
             "hd_context_get_timing",
             "hd_context_reserve", "hd_solve", "hd_solve_flx", "hd_solve_band", "hd_solve_host",
             "hd_solve_band_host", "hd_solve_radiance", "hd_solve_rays", "hd_quadrature",
-            "hd_chunk_solves", "hd_solve_spher", "hd_solve_flx_spher")
+            "hd_chunk_solves", "hd_solve_spher", "hd_solve_flx_spher", "hd_solve_rays_spher")
 
 # every symbol include/hdharp.h declares (harp-side steps around the solve)
 HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rfm_attenuate",
@@ -144,6 +144,10 @@ def load(path: str = LIB_PATH):
     lib.hd_solve_flx_spher.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                        ctypes.POINTER(HdInputs), ctypes.POINTER(HdSphere),
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.hd_solve_rays_spher.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                        ctypes.POINTER(HdInputs), ctypes.POINTER(HdSphere),
+                                        ctypes.POINTER(HdRays), ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_solve_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                   ctypes.POINTER(HdInputs), ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_solve_band_host.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
@@ -316,6 +320,18 @@ class Context:
                                   ctypes.c_void_p(rad_ptr or 0),
                                   ctypes.c_void_p(status_ptr or 0),
                                   ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def solve_rays_spher(self, cfg: HdConfig, inp: HdInputs, sph: HdSphere, rays: HdRays,
+                         flux_ptr: int | None, rad_ptr: int | None, status_ptr: int | None,
+                         stream_ptr: int | None):
+        """hd_solve_rays_spher: solve_rays with the pseudo-spherical beam (nstr <= 16)."""
+        rc = load().hd_solve_rays_spher(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                        ctypes.byref(sph), ctypes.byref(rays),
+                                        ctypes.c_void_p(flux_ptr or 0),
+                                        ctypes.c_void_p(rad_ptr or 0),
+                                        ctypes.c_void_p(status_ptr or 0),
+                                        ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
     def beer_flux(self, cfg: HdConfig, inp: HdInputs, flux_ptr: int, status_ptr: int | None,

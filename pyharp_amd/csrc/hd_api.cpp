@@ -1371,11 +1371,15 @@ int validate_rad(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
 
 // rays = null: the grid call (rad->umu x rad->phi, host arrays, into uu).  rays given
 // (hd_solve_rays): rad is its view of them (numu = nray, nphi = 1, umu / phi unused),
-// uu is the per-wave ray output or null
+// uu is the per-wave ray output or null.  sph (hd_solve_rays_spher, nstr <= 16): the
+// pseudo-spherical beam -- hd_spher_kernel after the chunk's tauc / Planck prologue, with
+// ch requested, and hd_rad_spher.hip's kernels.  keep_status: a solve of the same call
+// already ran on `stream` and its status bits stay (hd_solve_rays_spher's level fluxes)
 int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
                 const hd_radiance* rad, const hd_rays* rays, double* flux, double* uu,
-                int*& status, hipStream_t stream) {
-  const char* who = rays ? "hd_solve_rays" : "hd_solve_radiance";
+                int*& status, hipStream_t stream, const hd_sphere* sph = nullptr,
+                bool keep_status = false) {
+  const char* who = rays ? (sph ? "hd_solve_rays_spher" : "hd_solve_rays") : "hd_solve_radiance";
   int rc = HD_OK;
   const int nn = cfg->nstr / 2;
   const bool radiances = rad->onlyfl == 0;
@@ -1418,12 +1422,15 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
   // the intensity kernels keep the register-path layer record layout at every
   // nstr (hd::layer_record_doubles gives the team layout above nstr 16)
   const hd::RadPlan plan(nn, nlyr, planck, nm_mode, ntau, numu, hd::rad_layer_record_doubles(nn),
-                         hd::rad_rec_doubles(nn), hd::rad_bsub_doubles(nn), nsolve, ctx->chunk);
+                         hd::rad_rec_doubles(nn), hd::rad_bsub_doubles(nn), nsolve, ctx->chunk,
+                         /*spher=*/sph != nullptr);
   rc = ensure_scratch(ctx, who, plan.total);
   if (rc) return rc;
   if (!status && (rc = own_status(ctx, who, (size_t)nsolve, status))) return rc;
-  HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
-  HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
+  if (!keep_status) {
+    HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
+    HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
+  }
 
   double* const q = ctx->scratch;
   double *r_sw = q + plan.sw, *r_rd = q + plan.rd, *r_bs = q + plan.bs, *r_lev = q + plan.lev,
@@ -1436,6 +1443,35 @@ int rad_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
     const hd::PlanckArgs pa = planck_args(cfg, in, r_planck, s0, ns);
     HD_HIP(ctx, hd::launch_prologue(planck ? &pa : nullptr, beam ? &ta : nullptr, stream));
     hd::RadArgs a{};
+    if (sph) {  // ch' [nlyr+2] | lambda [nlyr] | ch [nlyr+1] | staging [2][nlyr], stride ns
+      double* r_sph = q + plan.sph;
+      hd::SpherProArgs xa{};
+      xa.prop = in->prop;
+      xa.fbeam = in->fbeam;
+      xa.umu0 = in->umu0;
+      xa.zd = sph->zd;
+      xa.chp = r_sph;
+      xa.lam = r_sph + (size_t)(nlyr + 2) * ns;
+      xa.ch = r_sph + (size_t)(2 * nlyr + 2) * ns;
+      xa.dts = r_sph + (size_t)(3 * nlyr + 3) * ns;
+      xa.status = status;
+      xa.anyerr = ctx->anyerr;
+      xa.radius = sph->radius;
+      xa.s0 = s0;
+      xa.nsc = ns;
+      xa.nlyr = nlyr;
+      xa.nprop = cfg->nprop;
+      xa.use_f = ta.use_f;
+      xa.f_slot = ta.f_slot;
+      xa.cmaj = 0;
+      xa.nwave = in->nwave;
+      xa.ncol = in->ncol;
+      xa.per_column = sph->per_column ? 1 : 0;
+      HD_HIP(ctx, hd::launch_spher_prologue(xa, stream));
+      a.chp = xa.chp;
+      a.lam = xa.lam;
+      a.ch = xa.ch;
+    }
     a.prop = in->prop;
     a.fbeam = in->fbeam;
     a.umu0 = in->umu0;
@@ -1531,6 +1567,55 @@ int hd_solve_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
       },
       [&](int*& st, hipStream_t s) {
         return rad_enqueue(ctx, cfg, in, &view, rays, flux, rad, st, s);
+      });
+}
+
+int hd_solve_rays_spher(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                        const hd_sphere* sph, const hd_rays* rays, double* flux, double* rad,
+                        int* status, void* stream) {
+  hd_radiance view{};  // the rays as hd_solve_radiance's user grid
+  return solve_entry(
+      ctx, "hd_solve_rays_spher", in, status, stream,
+      [&] {
+        const char* who = "hd_solve_rays_spher";
+        if (!rays) return fail(ctx, HD_EINVAL, "%s: null ray config", who);
+        if (!rad && !rays->brad)
+          return fail(ctx, HD_EINVAL, "%s: rad and brad both NULL: nothing to compute", who);
+        if (rays->brad && !rays->weight) return fail(ctx, HD_EINVAL, "%s: brad needs weight", who);
+        if (rays->nray < 1 || !rays->umu || !rays->phi)
+          return fail(ctx, HD_EINVAL, "%s: rays need nray >= 1, umu and phi", who);
+        if (rays->per_column != 0 && rays->per_column != 1)
+          return fail(ctx, HD_EINVAL, "%s: per_column=%d must be 0 or 1", who, rays->per_column);
+        int rc = check_sphere(ctx, sph, who);
+        if (rc) return rc;
+        if (cfg && cfg->nstr > 2 * hd::kMaxRegNN)
+          return fail(ctx, HD_EINVAL,
+                      "%s: nstr=%d; pseudo-spherical ray radiances support nstr <= %d", who,
+                      cfg->nstr, 2 * hd::kMaxRegNN);
+        view.ntau = rays->ntau;
+        view.utau = rays->utau;
+        view.numu = rays->nray;
+        view.nphi = 1;
+        view.phi0 = rays->phi0;
+        view.onlyfl = 0;
+        view.corint = rays->corint;
+        return validate_rad(ctx, cfg, in, &view, flux, rad ? rad : rays->brad, /*rays=*/true);
+      },
+      [&](int*& st, hipStream_t s) {
+        // Fluxes at the layer boundaries are hd_solve_spher's own: the flux solve runs
+        // first on the same stream and scratch, so one model's two outputs -- the fluxes
+        // of a flux module and those along the rays -- are the same numbers, bit for bit.
+        // Fluxes at user depths (utau) come from the intensity path's flux kernel.
+        const bool level_flux = flux && rays->ntau == 0;
+        if (level_flux) {
+          if (ctx->capturing)
+            return fail(ctx, HD_EINVAL,
+                        "hd_solve_rays_spher: not capturable into a HIP graph (host user grid)");
+          const int rc = solve_enqueue(ctx, cfg, in, flux, nullptr, nullptr, st, s, sph);
+          if (rc) return rc;
+        }
+        return rad_enqueue(ctx, cfg, in, &view, rays, level_flux ? nullptr : flux, rad, st, s, sph,
+                           /*keep_status=*/level_flux);
       });
 }
 

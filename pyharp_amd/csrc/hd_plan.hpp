@@ -195,20 +195,22 @@ inline size_t solve_reserve_doubles(int nn, int nlyr, bool planck, long chunk) {
 // ---- scratch of the intensity solves (hd_solve_radiance, hd_solve_rays) ---------------
 
 // rec_sw / rec_rd / rec_bs: doubles per (unit, layer) of the sweep, radiance and
-// back-substitution records (hd_rad.hpp); a solve is nm units (azimuthal modes)
+// back-substitution records (hd_rad.hpp); a solve is nm units (azimuthal modes).
+// spher (hd_solve_rays_spher only): the prologue's slant depths and secants,
+// spher_doubles(nlyr) per solve, after the Planck region
 struct RadPlan {
   size_t per_solve;  // modes x (per-unit records + radiance per mode) + prologue
   long chunk;
-  size_t sw, rd, bs, lev, cst, radm, taus, tauc, planck;  // offsets (doubles)
+  size_t sw, rd, bs, lev, cst, radm, taus, tauc, planck, sph;  // offsets (doubles)
   size_t total;
 
   RadPlan(int nn, int nlyr, bool planck_, int nm, int ntau, int numu, size_t rec_sw,
-          size_t rec_rd, size_t rec_bs, long nsolve, long max_chunk) {
+          size_t rec_rd, size_t rec_bs, long nsolve, long max_chunk, bool spher = false) {
     const size_t u_sw = (size_t)nlyr * rec_sw, u_rd = (size_t)nlyr * rec_rd,
                  u_bs = (size_t)nlyr * rec_bs, u_lev = (size_t)(nlyr + 1) * 2 * nn,
                  u_cst = (size_t)nlyr * 2 * nn, u_radm = (size_t)ntau * numu;
     per_solve = (size_t)nm * (u_sw + u_rd + u_bs + u_lev + u_cst + u_radm) + (size_t)(nlyr + 1) +
-                nlyr + (planck_ ? (size_t)nlyr + 3 : 0);
+                nlyr + (planck_ ? (size_t)nlyr + 3 : 0) + (spher ? spher_doubles(nlyr) : 0);
     // 16 GB of the 288 GB: chunks of ~1e5 units keep every SIMD busy in the per-unit sweep
     const double budget = 16.0 * 1024.0 * 1024.0 * 1024.0 / 8.0;  // doubles
     chunk = std::max<long>(1, std::min<long>(nsolve, (long)(budget / (double)per_solve)));
@@ -224,7 +226,8 @@ struct RadPlan {
     radm = q, q += u_radm * nuc;
     taus = q, q += (size_t)(nlyr + 1) * chunk;
     tauc = q, q += (size_t)nlyr * chunk;
-    planck = q;
+    planck = q, q += (planck_ ? (size_t)nlyr + 3 : 0) * chunk;
+    sph = q;
     total = per_solve * (size_t)chunk;
   }
 };

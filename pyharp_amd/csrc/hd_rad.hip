@@ -29,6 +29,7 @@
 // NN-loop unrolled, the matrices in registers); nstr 18..32 takes the team kernels
 // of hd_team_mfma.hip and the rolled one-lane kernels of hd_rad_wide.hip, launched
 // from the one sequence at the end of this file.  Record layouts: hd_rad_layout.hpp.
+// hd_rad_spher.hip compiles this file a second time for the pseudo-spherical beam (kSpher).
 //
 // Formulation: DESIGN.md section 3b, mirrored in numpy by
 // tests/kernel_model_rad.py; oracle: oracle/disort_rad_np.py.
@@ -38,10 +39,24 @@
 
 #include "hd_rad.hpp"
 
+// This source is compiled in two forms, as hd_rad_lane.hpp is: as it stands, and from
+// hd_rad_spher.hip with HD_RAD_SPHER defined -- the beam-using one-lane kernels (layer,
+// sweep, const, flux, user_map, ray) with the pseudo-spherical beam of DESIGN.md section 3e
+// in namespace hd::spher, without the kernels that use no beam and without the launch
+// sequence.  kSpher is a constant of the translation unit, not a template parameter: the
+// plain kernels keep their names and their code.
+#ifndef HD_RAD_SPHER
+#define HD_RAD_SPHER 0
+#endif
+
 namespace hd {
+#if HD_RAD_SPHER
+namespace spher {
+#endif
 
 namespace {
 
+constexpr bool kSpher = HD_RAD_SPHER != 0;
 constexpr int kLayerBlockR = 256;
 // the layer kernel's records (operators for the sweep, radiance records for the const,
 // flux and user kernels): whole-line stores, read a kernel later -- nontemporal
@@ -59,6 +74,7 @@ __constant__ RadCoef c_rcoef;             // the Y_l^m recurrence coefficients
 // quad_r / tab_r / ylm_row / flag, hd_rad_const_kernel and hd_rad_flux_kernel, unrolled
 #include "hd_rad_lane.hpp"
 
+#if !HD_RAD_SPHER
 // ============================================================================
 // unscaled depth of every level, solver order (0 = top)
 // ============================================================================
@@ -77,10 +93,14 @@ __global__ __launch_bounds__(256) void hd_rad_taus_kernel(RadArgs A) {
   if (A.utau && A.ntau > 0 && A.utau[A.ntau - 1] > t * (1.0 + 1e-12) + 1e-300)
     flag(A, s, kStBadInput);  // user depth below the bottom
 }
+#endif  // !HD_RAD_SPHER
 
 // ============================================================================
 // per-(unit, layer) setup (hd_layer_kernel generalised to mode m)
 // ============================================================================
+// kSpher (pseudo-spherical beam): the beam's rate in this layer is
+// sph_beam's secant (any sign, or zero) in place of 1/mu0 and its amplitude at the layer
+// top exp(-ch'_top); Y_l^m(mu0) keeps the true mu0.
 template <int NN>
 __global__ __launch_bounds__(kLayerBlockR) void hd_rad_layer_kernel(RadArgs A) {
   constexpr int N = 2 * NN;
@@ -118,9 +138,16 @@ __global__ __launch_bounds__(kLayerBlockR) void hd_rad_layer_kernel(RadArgs A) {
 
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
   if (fb > 0.0 && !(mu0 > 0.0 && mu0 <= 1.0)) st |= kStBadInput;  // cdisort c_chekin
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  double chtop = 0.0;  // kSpher: slant depth of the beam at the layer top
+  if constexpr (kSpher) {
+    beam = beam && sph_beam_on(A, sl);
+    const SphBeam sb = sph_beam(A, lc, sl, taup);
+    rmu0 = beam ? sb.lam : 0.0;
+    chtop = sb.top;
+  }
   const double mub = beam ? mu0 : 0.0;
   const bool therm = A.planck && m == 0;
 
@@ -329,8 +356,13 @@ __global__ __launch_bounds__(kLayerBlockR) void hd_rad_layer_kernel(RadArgs A) {
     for (int i = 0; i < NN; ++i) y[i] = Qc.sd[i] * Qc.mu[i] * sv[i];
     lower_solve<NN>(lch, rdl, y);
     lower_t_solve<NN>(lch, rdl, y);
-    const double tauc = A.tauc[(size_t)lc * A.ns + sl];
-    const double att = 0.5 * exp(-tauc * rmu0);
+    double att;
+    if constexpr (kSpher) {
+      att = 0.5 * exp(-chtop);
+    } else {
+      const double tauc = A.tauc[(size_t)lc * A.ns + sl];
+      att = 0.5 * exp(-tauc * rmu0);
+    }
 #pragma unroll
     for (int i = 0; i < NN; ++i) {
       const double dd = Qc.rg[i] * fma(-y[i], rmu0, lxd[i]);
@@ -476,6 +508,7 @@ __global__ __launch_bounds__(kLayerBlockR) void hd_rad_layer_kernel(RadArgs A) {
 // ============================================================================
 // per-unit adding sweep + back-substitution keeping I+/I- at every level
 // ============================================================================
+// kSpher: the surface is lit by the beam at its slant depth, exp(-ch'_0)
 template <int NN>
 #ifndef HD_RAD_SWEEP_WAVES
 #define HD_RAD_SWEEP_WAVES 1
@@ -675,7 +708,12 @@ void hd_rad_sweep_kernel(RadArgs A) {
     for (int j = 0; j < NN; ++j) grg += Qc.g[i] * HD_SYM(ra, i, j) * Qc.g[j];
   }
   double esurf = (1.0 - alb) * bsurf;
-  if (beam) esurf += alb * f0mu0 * exp(-tauc * rmu0) / kPi;
+  if constexpr (kSpher) {  // the beam-on flag is read here, not held across the sweep
+    if (beam && sph_beam_on(A, sl))
+      esurf += alb * f0mu0 * exp(-A.chp[(size_t)L * A.ns + sl]) / kPi;
+  } else {
+    if (beam) esurf += alb * f0mu0 * exp(-tauc * rmu0) / kPi;
+  }
   const double x = (2.0 * alb * gsd + esurf) / (1.0 - 2.0 * alb * grg);
   double ip[NN];
   double chk = 0.0;
@@ -745,6 +783,9 @@ void hd_rad_sweep_kernel(RadArgs A) {
 #define HD_RAD_UMAP_UTAU_REG 1
 #endif
 constexpr bool kUmapUtauReg = HD_RAD_UMAP_UTAU_REG != 0;
+// kSpher: the beam source of layer lc is ab exp(-lam t) with sph_beam's secant (the maps
+// carry exp(-ch'_top) in ab); both whole-layer beam quotients, 1 + |mu| lam and
+// 1 - |mu| lam, can vanish and go through dexp
 template <int NN>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HD_RAD_UMAP_WAVES)))
 void hd_rad_user_map_kernel(RadArgs A) {
@@ -765,8 +806,9 @@ void hd_rad_user_map_kernel(RadArgs A) {
   const double muu = user_mu(A, s, iu);
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
+  if constexpr (kSpher) beam = beam && sph_beam_on(A, sl);
+  double rmu0 = beam ? 1.0 / mu0 : 0.0;  // kSpher: the layer's secant, set per layer
   const bool therm = A.planck && m == 0;
   const int par = m & 1;
   double ye[NN], yo[NN];
@@ -790,7 +832,9 @@ void hd_rad_user_map_kernel(RadArgs A) {
       for (int i = 0; i < NN; ++i) fdn = fma(Qc.g[i] * Qc.g[i], lv[(RadLev<NN>::Im + i) * nu], fdn);
       fdn *= 2.0 * kPi;
       const double alb = A.albedo ? A.albedo[s] : 0.0;
-      if (beam) {
+      if constexpr (kSpher) {
+        if (beam) fdn += fb * mu0 * exp(-A.chp[(size_t)L * A.ns + sl]);
+      } else if (beam) {
         const double tb = A.tauc[(size_t)(L - 1) * A.ns + sl] +
                           RadAt<NN>::rec(A.rrd, R::size, L - 1, nu, u)[R::Tp * nu];
         fdn += fb * mu0 * exp(-tb * rmu0);
@@ -817,6 +861,7 @@ void hd_rad_user_map_kernel(RadArgs A) {
     const double* m2 = RadAt<NN>::rec(A.bsub, RadBsub<NN>::size, lc, nu, u);
     const double* co = RadElemMajor::rec(A.cst, C::size, lc, nu, u);
     const double bt = rr[R::Bt * nu], slope = rr[R::Sl * nu], taup = rr[R::Tp * nu];
+    if constexpr (kSpher) rmu0 = beam ? sph_beam(A, lc, sl, taup).lam : 0.0;
     double kk[NN], hpl[NN], hmi[NN];
 #pragma unroll
     for (int j = 0; j < NN; ++j) {
@@ -885,8 +930,12 @@ void hd_rad_user_map_kernel(RadArgs A) {
     }
     if (beam) {
       const double e0l = rr[R::E0 * nu];
-      lay += up ? ab * (1.0 - e0l * emu) / fma(anu, rmu0, 1.0)
-                : ab * dexp(e0l, emu, fma(-anu, rmu0, 1.0), lmu);
+      if constexpr (kSpher)
+        lay += up ? ab * dexp(1.0, e0l * emu, fma(anu, rmu0, 1.0), lmu)
+                  : ab * dexp(e0l, emu, fma(-anu, rmu0, 1.0), lmu);
+      else
+        lay += up ? ab * (1.0 - e0l * emu) / fma(anu, rmu0, 1.0)
+                  : ab * dexp(e0l, emu, fma(-anu, rmu0, 1.0), lmu);
     }
     if (therm) {
       lay += up ? (a0 + a1t * muu) - (a0 + a1t * taup + a1t * muu) * emu
@@ -918,6 +967,7 @@ void hd_rad_user_map_kernel(RadArgs A) {
   if (!isfinite(chk)) flag(A, s, kStNonFinite);
 }
 
+#if !HD_RAD_SPHER
 // ============================================================================
 // uu[s][j][lu][iu] = sum_m I_m cos(m (phi_j - phi0))
 // ============================================================================
@@ -939,6 +989,7 @@ __global__ __launch_bounds__(256) void hd_rad_azimuth_kernel(RadArgs A) {
   for (int m = 0; m < A.nm; ++m) acc = fma(src[(size_t)m * A.ns], cos(m * dphi), acc);
   A.uu[(((size_t)s * A.nphi + j) * A.ntau + lu) * A.numu + iu] = acc;
 }
+#endif  // !HD_RAD_SPHER
 
 
 // ============================================================================
@@ -952,6 +1003,8 @@ __global__ __launch_bounds__(256) void hd_rad_azimuth_kernel(RadArgs A) {
 // (moments 2 g - g^2).  Same arithmetic as oracle/disort_rad_np.py's
 // ims_correction / xi_func.  mu1 = |mu| of a downward user direction.
 // ============================================================================
+// mu0: the beam's cosine through the slab -- the true mu0, or under the pseudo-spherical
+// beam the slab's mean cosine tu / ch(tu) (tms_sum); cos(Theta) in ct keeps the true mu0.
 __device__ double ims_term(const RadArgs& A, long s, int nstr, double ct, double mu1, double mu0,
                            double tu, int lu_l) {
   constexpr double kTiny = 1.0e-4;
@@ -1025,6 +1078,10 @@ __device__ double ims_term(const RadArgs& A, long s, int nstr, double ct, double
 // ============================================================================
 // the bracket of the correction at one direction (mu, phi [deg]) and user depth lu of
 // solve s = s0 + sl with a beam (fb > 0, mu0 > 0); the correction is fb/(4 pi) times it
+// kSpher: the beam at scaled depth t of layer lc is exp(-(top + lam (t - top_lc))) of
+// sph_beam in place of exp(-t/mu0), so den = 1 + lam mu with the same series branch, and
+// the IMS step takes the mean cosine of the slab above the user depth, tu / ch(tu), ch the
+// unscaled slant depth, linear in tau inside the user's layer
 __device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int lu, double mu,
                                           double phi, double mu0, double fb, int nstr) {
   const int L = A.nlyr, np = A.nprop, nm = A.nmom;
@@ -1036,7 +1093,7 @@ __device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int 
   const double tu = user_tau(A, lu, sl);
   int lu_l = 0;
   while (lu_l < L - 1 && tu > A.taus[(size_t)(lu_l + 1) * A.ns + sl]) ++lu_l;
-  const double rmu0 = 1.0 / mu0;
+  double rmu0 = 1.0 / mu0;  // kSpher: the layer's secant, set per layer
   double acc = 0.0, tau_u = 0.0;
   for (int pass = 0; pass < 2; ++pass) {  // pass 0: scaled depth of the user level
     const int lo = pass == 0 ? lu_l : (mu > 0.0 ? lu_l : 0);
@@ -1058,6 +1115,12 @@ __device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int 
       const double bot = top + taup;
       const double t1 = mu > 0.0 ? fmax(tau_u, top) : fmin(tau_u, bot);
       const double t2 = mu > 0.0 ? bot : top;
+      double b0 = 0.0;  // the beam at depth t of this layer is exp(-(b0 + rmu0 t))
+      if constexpr (kSpher) {
+        const SphBeam sb = sph_beam(A, lc, sl, taup);
+        rmu0 = sb.lam;
+        b0 = fma(-sb.lam, top, sb.top);
+      }
       // phase functions at cos(Theta): full series and delta-M truncated series
       double pa = 1.0, pm = 1.0;  // k = 0 terms: chi_0 = 1, (chi_0 - f)/(1 - f) = 1
       double p1 = 1.0, p2 = 0.0;
@@ -1073,7 +1136,8 @@ __device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int 
       const double om = ssa * (1.0 - f) / (1.0 - ssa * f);
       const double w = ssa * pa / (1.0 - f * ssa) - om * pm;
       // int_{t1}^{t2} e^{-t/mu0} e^{-(t - tau_u)/mu} dt/mu
-      const double e1 = exp(-t1 * rmu0 - (t1 - tau_u) / mu);
+      const double e1 = kSpher ? exp(-fma(t1, rmu0, b0) - (t1 - tau_u) / mu)
+                              : exp(-t1 * rmu0 - (t1 - tau_u) / mu);
       const double den = fma(rmu0, mu, 1.0);
       const double x = den * (t2 - t1) / mu;
       double seg;
@@ -1081,15 +1145,28 @@ __device__ __forceinline__ double tms_sum(const RadArgs& A, long s, int sl, int 
         const double phx = x == 0.0 ? 1.0 : -expm1(-x) / x;
         seg = e1 * (t2 - t1) / mu * phx;
       } else {
-        seg = (e1 - exp(-t2 * rmu0 - (t2 - tau_u) / mu)) / den;
+        seg = (e1 - (kSpher ? exp(-fma(t2, rmu0, b0) - (t2 - tau_u) / mu)
+                           : exp(-t2 * rmu0 - (t2 - tau_u) / mu))) / den;
       }
       acc = fma(w, seg, acc);
     }
+  }
+  if constexpr (kSpher) {
+    if (mu < 0.0 && fb > 1.0e-4) {
+      const double ttop = A.taus[(size_t)lu_l * A.ns + sl];
+      const double dtl = A.taus[(size_t)(lu_l + 1) * A.ns + sl] - ttop;
+      const double c0 = A.ch[(size_t)lu_l * A.ns + sl], c1 = A.ch[(size_t)(lu_l + 1) * A.ns + sl];
+      const double chu = dtl > 0.0 ? fma(c1 - c0, fmin(fmax((tu - ttop) / dtl, 0.0), 1.0), c0) : c0;
+      const double mub = chu > 0.0 ? fmin(tu / chu, 1.0) : mu0;
+      acc -= ims_term(A, s, nstr, ct, -mu, mub, tu, lu_l);
+    }
+    return acc;
   }
   if (mu < 0.0 && fb > 1.0e-4) acc -= ims_term(A, s, nstr, ct, -mu, mu0, tu, lu_l);  // SECSCA: fbeam > tiny
   return acc;
 }
 
+#if !HD_RAD_SPHER
 __global__ __launch_bounds__(256) void hd_rad_tms_kernel(RadArgs A, int nstr) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n = (long)A.ns * A.nphi * A.ntau * A.numu;
@@ -1107,6 +1184,7 @@ __global__ __launch_bounds__(256) void hd_rad_tms_kernel(RadArgs A, int nstr) {
   const double acc = tms_sum(A, s, sl, lu, A.umu[iu], A.phi[j], mu0, fb, nstr);
   A.uu[(((size_t)s * A.nphi + j) * A.ntau + lu) * A.numu + iu] += fb / (4.0 * kPi) * acc;
 }
+#endif  // !HD_RAD_SPHER
 
 // ============================================================================
 // ray epilogue (hd_solve_rays): user angle r of a solve is one outgoing ray with its
@@ -1134,7 +1212,9 @@ __device__ __forceinline__ double ray_radiance(const RadArgs& A, int sl, int lu,
   if (A.corint && A.tauc) {
     const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
     const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-    if (fb > 0.0 && mu0 > 0.0)
+    bool beam = fb > 0.0 && mu0 > 0.0;
+    if constexpr (kSpher) beam = beam && sph_beam_on(A, sl);
+    if (beam)
       acc = fma(fb / (4.0 * kPi), tms_sum(A, s, sl, lu, mu, phi, mu0, fb, nstr), acc);
   }
   return acc;
@@ -1174,6 +1254,7 @@ __global__ __launch_bounds__(256) void hd_rad_ray_kernel(RadArgs A, int nstr) {
   }
 }
 
+#if !HD_RAD_SPHER
 __global__ __launch_bounds__(256) void hd_ray_cosines_kernel(const double* umu, double* out,
                                                              long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1187,6 +1268,7 @@ hipError_t launch_ray_cosines(const double* umu, double* out, long n, hipStream_
                      stream, umu, out, n);
   return hipGetLastError();
 }
+#endif  // !HD_RAD_SPHER
 
 // ============================================================================
 // host side
@@ -1198,14 +1280,39 @@ hipError_t upload_rad_tables(const QuadHost* per_nn) {
   static RadCoef coef;
   fill_rad(c, per_nn);
   fill_rad_coef(coef);
-  // the nstr 18..32 instantiations keep their own tables (hd_rad_wide.hip)
-  hipError_t e = wide::upload_rad_tables(per_nn);
+  hipError_t e = hipSuccess;
+#if !HD_RAD_SPHER
+  // the nstr 18..32 instantiations keep their own tables (hd_rad_wide.hip), and so do the
+  // pseudo-spherical ones of nstr <= 16 (hd_rad_spher.hip)
+  e = wide::upload_rad_tables(per_nn);
   if (e != hipSuccess) return e;
+  e = spher::upload_rad_tables(per_nn);
+  if (e != hipSuccess) return e;
+#endif
   e = hipMemcpyToSymbol(HIP_SYMBOL(c_rcoef), &coef, sizeof(RadCoef));
   if (e != hipSuccess) return e;
   return hipMemcpyToSymbol(HIP_SYMBOL(c_rad), &c, sizeof(c));
 }
 
+// the one-lane kernels of this file at one NN <= kMaxRegNN (null above it: the team and
+// rolled launchers run there) and the ray epilogues of every nstr, in this translation
+// unit's form
+RegKernels reg_kernels(int nn) {
+  RegKernels k{};
+  k.ray = hd_rad_ray_kernel<false>;
+  k.ray_band = hd_rad_ray_kernel<true>;
+  (void)dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
+    k.layer = hd_rad_layer_kernel<NN>;
+    k.sweep = hd_rad_sweep_kernel<NN>;
+    k.cst = hd_rad_const_kernel<NN>;
+    k.flux = hd_rad_flux_kernel<NN>;
+    k.user_map = hd_rad_user_map_kernel<NN>;
+    return hipSuccess;
+  });
+  return k;
+}
+
+#if !HD_RAD_SPHER
 // HD_RAD_USER=rolled: nstr 18..32 user angles by the one-lane-per-(unit, angle) kernel
 static bool rad_user_rolled() {
   static const bool v = [] {
@@ -1215,31 +1322,17 @@ static bool rad_user_rolled() {
   return v;
 }
 
-// the one-lane kernels of this file at one NN <= kMaxRegNN
-struct RegKernels {
-  void (*layer)(RadArgs);
-  void (*sweep)(RadArgs);
-  void (*cst)(RadArgs);
-  void (*flux)(RadArgs);
-  void (*user_map)(RadArgs);
-};
-static RegKernels reg_kernels(int nn) {
-  RegKernels k{};
-  (void)dispatch_nn<1, kMaxRegNN>(nn, [&](auto NN) {
-    k = {hd_rad_layer_kernel<NN>, hd_rad_sweep_kernel<NN>, hd_rad_const_kernel<NN>,
-         hd_rad_flux_kernel<NN>, hd_rad_user_map_kernel<NN>};
-    return hipSuccess;
-  });
-  return k;
-}
-
 // One chunk of the intensity path, nstr 2..32.  Each stage is the one-lane kernel of
 // this file (reg: nstr <= 16), or at nstr 18..32 the team launcher (hd_team_mfma.hip)
 // or the rolled one-lane launcher (hd_rad_wide.hip).
 hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_t st) {
   if (nn < 1 || nn > kRadMaxNN) return hipErrorInvalidValue;
   const bool reg = nn <= kMaxRegNN;
-  const RegKernels k = reg_kernels(nn);  // null pointers at nn > kMaxRegNN, not launched
+  // the pseudo-spherical beam (a.chp given): the paired-ray call at nstr <= 16 only, with
+  // hd_spher_kernel's three arrays (the prologue ran with ch requested)
+  const bool spher = a.chp != nullptr;
+  if (spher && !(reg && a.ray_umu && a.lam && a.ch)) return hipErrorInvalidValue;
+  const RegKernels k = spher ? spher::reg_kernels(nn) : reg_kernels(nn);
   // the launchers of the other sources return (and clear) their launch error: keep the first
   hipError_t err = hipSuccess;
   auto keep = [&](hipError_t e) {
@@ -1293,12 +1386,10 @@ hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_
       keep(wide::launch_rad_user(nn, a, st));
     if (a.ray_umu) {
       const long ny = (long)a.ntau * a.numu;
-      if (a.brad)
-        hipLaunchKernelGGL(hd_rad_ray_kernel<true>, dim3((unsigned)((a.ncol * ny + 255) / 256)),
-                           dim3(256), 0, st, a, 2 * nn);
-      else
-        hipLaunchKernelGGL(hd_rad_ray_kernel<false>, dim3((unsigned)((a.ns * ny + 255) / 256)),
-                           dim3(256), 0, st, a, 2 * nn);
+      void (*ray)(RadArgs, int) = a.brad ? k.ray_band : k.ray;
+      const long nx = a.brad ? a.ncol : a.ns;
+      hipLaunchKernelGGL(ray, dim3((unsigned)((nx * ny + 255) / 256)), dim3(256), 0, st, a,
+                         2 * nn);
       keep(hipGetLastError());
       return err;
     }
@@ -1312,5 +1403,9 @@ hipError_t launch_rad_chunk(int nn, const RadArgs& a, bool radiances, hipStream_
   keep(hipGetLastError());
   return err;
 }
+#endif  // !HD_RAD_SPHER
 
+#if HD_RAD_SPHER
+}  // namespace spher
+#endif
 }  // namespace hd

@@ -2,6 +2,8 @@
 // azimuthal mode, user optical depths and user angles, nstr <= 32.  A unit is one
 // (solve, mode) problem.  Which kernel exists in which form:
 //   hd_rad.hip       the kernels without NN (taus, azimuth, tms, ray, ray cosines);
+//                    (hd_rad_spher.hip compiles its beam-using kernels a second time, with
+//                    the pseudo-spherical beam, into hd::spher)
 //                    nstr <= 16 only, NN-loops unrolled, one lane per unit: layer,
 //                    sweep, user_map; the chunk's launch sequence for every nstr
 //   hd_rad_lane.hpp  const and flux, one lane per problem at every nstr: unrolled in
@@ -74,7 +76,36 @@ struct RadArgs {
   const double* weight;   // rays: [nwave] band weights or null
   double* rad;            // rays: [S][ntau][numu] or null
   double* brad;           // rays: [ncol][ntau][numu] or null (needs weight)
+  // pseudo-spherical beam (hd_solve_rays_spher): hd_spher_kernel's
+  // slant depths and secants of the chunk (SphArgs' layout, stride ns), read by the nstr <= 16
+  // kernels of hd_rad_spher.hip only; null = the plane-parallel beam
+  const double* chp;  // [nlyr+2][ns] scaled slant depth ch' per level; row nlyr+1: beam on
+  const double* lam;  // [nlyr][ns]   secant of the beam's one exponential per layer
+  const double* ch;   // [nlyr+1][ns] unscaled slant depth per level (the IMS step)
 };
+
+// The pseudo-spherical beam inside solver layer lc of chunk solve sl (hd_rad_spher.hip): in
+// the layer's own scaled depth t in [0, taup] it is exp(-(top + lam t)).  top is ch' of
+// the layer's upper level and lam hd_spher_kernel's secant -- except where ch' falls by
+// more than kE0Cap through the layer (hd_device.hpp): there the beam is the one that
+// reaches the exact exp(-ch'_bottom) with the transmission held at exp(kE0Cap).
+struct SphBeam {
+  double lam, top;
+};
+__device__ __forceinline__ SphBeam sph_beam(const RadArgs& A, int lc, int sl, double taup) {
+  const double ct = A.chp[(size_t)lc * A.ns + sl];
+  const double cb = A.chp[(size_t)(lc + 1) * A.ns + sl];
+  SphBeam b{A.lam[(size_t)lc * A.ns + sl], ct};
+  if (taup > 0.0 && ct - cb > kE0Cap) {
+    b.lam = -kE0Cap / taup;
+    b.top = cb + kE0Cap;
+  }
+  return b;
+}
+// whether the pseudo-spherical beam of chunk solve sl is on (a valid zd, fbeam > 0, umu0 > 0)
+__device__ __forceinline__ bool sph_beam_on(const RadArgs& A, int sl) {
+  return A.chp[(size_t)(A.nlyr + 1) * A.ns + sl] != 0.0;
+}
 
 // int_{t1}^{t2} a exp(-c (t - tref)) exp(-(t - t1)/mu) dt/mu, t1 = evaluation
 // depth, (t2 - t1)/mu >= 0; the 1 + c mu -> 0 limit through (1 - e^-x)/x
@@ -154,6 +185,25 @@ inline void fill_rad(RadTabs<LO, HI>& c, const QuadHost* per_nn) {
   fill_rad_tables(LO, per_nn[LO - 1].mu, &c.t.lam[0][0][0]);
   if constexpr (LO < HI) fill_rad(c.next, per_nn);
 }
+
+// the one-lane kernels of hd_rad.hip at one NN <= kMaxRegNN (null above it) and its two
+// ray epilogues (every nstr)
+struct RegKernels {
+  void (*layer)(RadArgs);
+  void (*sweep)(RadArgs);
+  void (*cst)(RadArgs);
+  void (*flux)(RadArgs);
+  void (*user_map)(RadArgs);
+  void (*ray)(RadArgs, int);
+  void (*ray_band)(RadArgs, int);
+};
+// nstr <= 16 with the pseudo-spherical beam (RadArgs::chp given): hd_rad.hip's beam-using
+// kernels compiled a second time, with HD_RAD_SPHER, from hd_rad_spher.hip -- the kernels
+// launch_rad_chunk takes then, and their tables
+namespace spher {
+hipError_t upload_rad_tables(const QuadHost* per_nn);
+RegKernels reg_kernels(int nn);
+}  // namespace spher
 
 hipError_t upload_rad_tables(const QuadHost* per_nn);  // nn 1..kRadMaxNN
 // tauc/planck prologue must have run (launch_prologue) for the chunk's solves;

@@ -5,7 +5,8 @@
 // unrolled and instantiates NN 1..8 (matrices in registers); hd_rad_wide.hip includes
 // it with them rolled, in hd::wide, and instantiates NN 9..16 (matrices in private
 // memory).  Include it inside the namespace, after hd_rad.hpp and after the source's
-// own tables in constant memory: RadTabs<LO, HI> c_rad and RadCoef c_rcoef.
+// own tables in constant memory, RadTabs<LO, HI> c_rad and RadCoef c_rcoef, and its constant
+// bool kSpher (the pseudo-spherical beam: hd_rad_spher.hip alone sets it).
 // No include guard: one inclusion per translation unit.
 
 namespace {
@@ -79,6 +80,9 @@ HD_UNROLL_NN
   for (int j = 0; j < NN; ++j) kk[j] = rr[(R::K + j) * rs];
 }
 
+// kSpher (a constant of the including source; nstr <= 16 in hd_rad_spher.hip only): the
+// beam of the layer is exp(-(top + lam t)) of sph_beam (hd_rad.hpp) in place of
+// exp(-(tauc + t)/mu0)
 template <int NN>
 #ifndef HD_RAD_CONST_WAVES
 #define HD_RAD_CONST_WAVES 1
@@ -103,7 +107,13 @@ void hd_rad_const_kernel(RadArgs A) {
   const double bt = rr[R::Bt * rs], slope = rr[R::Sl * rs], taup = rr[R::Tp * rs];
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const double rmu0 = (fb > 0.0 && mu0 > 0.0) ? 1.0 / mu0 : 0.0;
+  double rmu0 = (fb > 0.0 && mu0 > 0.0) ? 1.0 / mu0 : 0.0;
+  double chtop = 0.0;  // kSpher: slant depth of the beam at the layer top
+  if constexpr (kSpher) {
+    const SphBeam sb = sph_beam(A, lc, sl, taup);
+    rmu0 = sph_beam_on(A, sl) ? sb.lam : 0.0;
+    chtop = sb.top;
+  }
   double cp[NN], cm[NN];
 HD_UNROLL_NN
   for (int side = 0; side < 2; ++side) {  // 0: layer top, 1: layer bottom
@@ -171,11 +181,14 @@ HD_UNROLL_NN
       const double f = nmo >= N ? q[1 + N] : 0.0;
       const double om = ssa * (1.0 - f) / (1.0 - ssa * f);
       const double rf = om / (1.0 - f);
-      const bool beam = fb > 0.0 && mu0 > 0.0;
+      bool beam = fb > 0.0 && mu0 > 0.0;
+      if constexpr (kSpher) beam = beam && sph_beam_on(A, sl);
       double y0[N];
       ylm_row<N>(m, beam ? mu0 : 0.0, y0);
       const double fac = (m == 0 ? 1.0 : 2.0) * fb / (4.0 * kPi);
-      const double eb = beam ? fac * exp(-A.tauc[(size_t)lc * A.ns + sl] * rmu0) : 0.0;
+      double eb;
+      if constexpr (kSpher) eb = beam ? fac * exp(-chtop) : 0.0;
+      else eb = beam ? fac * exp(-A.tauc[(size_t)lc * A.ns + sl] * rmu0) : 0.0;
       const int par = m & 1;
       const double* lam = &tab_r<NN>().lam[m][0][0];
       double zs[NN], zd[NN], hh[NN];
@@ -239,9 +252,12 @@ HD_UNROLL_NN
   }
 }
 
+
 // ============================================================================
 // fluxes at the user depths from the m = 0 field (unit u = sl)
 // ============================================================================
+// kSpher: the particular solution and the direct term mu0 F0 exp(-(top + lam t)) on
+// sph_beam's secant and slant depth
 template <int NN>
 __global__ __launch_bounds__(256) void hd_rad_flux_kernel(RadArgs A) {
   using R = RadRec<NN>;
@@ -268,8 +284,15 @@ __global__ __launch_bounds__(256) void hd_rad_flux_kernel(RadArgs A) {
   const double t = fmin(fmax((tu - ttop) * scale, 0.0), taup);
   const double mu0 = A.umu0 ? A.umu0[s] : 1.0;
   const double fb = A.fbeam ? A.fbeam[s] : 0.0;
-  const bool beam = fb > 0.0 && mu0 > 0.0;
-  const double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  bool beam = fb > 0.0 && mu0 > 0.0;
+  double rmu0 = beam ? 1.0 / mu0 : 0.0;
+  double chtop = 0.0;  // kSpher: slant depth of the beam at the layer top
+  if constexpr (kSpher) {
+    beam = beam && sph_beam_on(A, sl);
+    const SphBeam sb = sph_beam(A, lc, sl, taup);
+    rmu0 = beam ? sb.lam : 0.0;
+    chtop = sb.top;
+  }
   const double* co = RadElemMajor::rec(A.cst, RadCst<NN>::size, lc, nu, u);
   double al[NN], be[NN];
 HD_UNROLL_NN
@@ -312,9 +335,16 @@ HD_UNROLL_NN
   }
   up *= 2.0 * kPi;
   dn *= 2.0 * kPi;
-  if (beam) dn += fb * mu0 * exp(-(A.tauc[(size_t)lc * A.ns + sl] + t) * rmu0);
+  if constexpr (kSpher) {
+    // (user depths only: at the layer boundaries hd_solve_rays_spher takes the fluxes from
+    // the flux solve, where the level below a layer of zero depth has its own ch')
+    if (beam) dn += fb * mu0 * exp(-fma(rmu0, t, chtop));
+  } else {
+    if (beam) dn += fb * mu0 * exp(-(A.tauc[(size_t)lc * A.ns + sl] + t) * rmu0);
+  }
   double* fo = A.flux + ((size_t)s * A.ntau + (A.ntau - 1 - lu)) * 2;
   fo[0] = up;
   fo[1] = dn;
   if (!isfinite(up + dn)) flag(A, s, kStNonFinite);
 }
+

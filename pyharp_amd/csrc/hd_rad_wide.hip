@@ -22,6 +22,7 @@ namespace {
 
 __constant__ RadTabs<kMaxRegNN + 1, kRadMaxNN> c_rad;  // quadrature, Y_l^m table of NN 9..16
 __constant__ RadCoef c_rcoef;                          // the Y_l^m recurrence coefficients
+constexpr bool kSpher = false;  // the rolled kernels have no pseudo-spherical form
 
 }  // namespace
 

@@ -387,7 +387,8 @@ class Disort(RTSolver):
                      temf: Optional[torch.Tensor] = None, *, umu: torch.Tensor,
                      phi: torch.Tensor, out: Optional[torch.Tensor] = None,
                      flux: Optional[torch.Tensor] = None,
-                     status: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     status: Optional[torch.Tensor] = None,
+                     zd: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Radiances (nwave, ncol, ntau, nray) along nray paired outgoing directions
         (hd_solve_rays): ``umu`` / ``phi`` are float64 tensors (nray,) -- shared by every
         column -- or (ncol, nray) -- each column's own rays; umu the polar cosine
@@ -401,9 +402,19 @@ class Disort(RTSolver):
         are staged with torch copies and the result comes back on the CPU; caller-supplied
         ``out`` / ``flux`` / ``status`` buffers are written by the device and must be on the
         solve device (``cuda:<options.device()>`` for CPU inputs), as for ``forward``.  A ray with umu = 0, |umu| > 1 or
-        a non-finite umu fails its column's solves (HD_STATUS_BAD_INPUT) and is NaN."""
+        a non-finite umu fails its column's solves (HD_STATUS_BAD_INPUT) and is NaN.
+
+        ``zd`` given: the pseudo-spherical beam (hd_solve_rays_spher)
+        with ``DisortOptions.radius`` as the planet radius -- the level altitudes above it,
+        bottom -> top, a float64 tensor (nlyr+1,) shared by all columns or (ncol, nlyr+1),
+        staged to the solve device like ``umu``.  nstr <= 16.  The 'spher' flag is not
+        needed (and cannot be set on a module with radiances); without ``zd`` the call is
+        the plane-parallel one.  A column whose zd is not finite or not strictly increasing
+        fails its solves (HD_STATUS_BAD_INPUT), which run with the beam off.  ``flux`` at the
+        layer boundaries (no ``usrtau``) is then the flux solve's own output, bitwise
+        ``forward(zd=)`` of an 'onlyfl,spher' module on the same inputs."""
         try:
-            return self._forward_rays(prop, bc, temf, umu, phi, out, flux, status, None)
+            return self._forward_rays(prop, bc, temf, umu, phi, out, flux, status, None, zd)
         except RuntimeError as err:
             if "at least one solve failed" in str(err) and _beam_hint(bc):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
@@ -416,21 +427,23 @@ class Disort(RTSolver):
                           out: Optional[torch.Tensor] = None,
                           rad: Optional[torch.Tensor] = None,
                           flux: Optional[torch.Tensor] = None,
-                          status: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          status: Optional[torch.Tensor] = None,
+                          zd: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The band radiance (ncol, ntau, nray) = sum_w weights[w] rad_w of
         ``forward_rays``, with the sum fused into the solve (the legacy driver's
         ``btoa(n) += wght[b] * toa(b, n)``).  Per-wave radiances are stored only if
         ``rad`` (nwave, ncol, ntau, nray) is given.  One fma per wave in wave order, no
-        atomics: bitwise equal to ``spectral.band_rad(forward_rays(...), weights)``."""
+        atomics: bitwise equal to ``spectral.band_rad(forward_rays(...), weights)``.
+        ``zd``: as ``forward_rays`` (the pseudo-spherical beam)."""
         try:
             return self._forward_rays(prop, bc, temf, umu, phi, rad, flux, status,
-                                      (weights, out))
+                                      (weights, out), zd)
         except RuntimeError as err:
             if "at least one solve failed" in str(err) and _beam_hint(bc):
                 raise RuntimeError(str(err) + _beam_hint(bc)) from err
             raise
 
-    def _forward_rays(self, prop, bc, temf, umu, phi, rad, flux, status, band):
+    def _forward_rays(self, prop, bc, temf, umu, phi, rad, flux, status, band, zd=None):
         import ctypes
         who = "Disort.forward_rays" + ("_band" if band is not None else "")
         ds = self.options.ds()
@@ -441,6 +454,20 @@ class Disort(RTSolver):
             raise RuntimeError(f"{who}: prop must be (nwave, ncol, nlyr, nprop), got "
                                f"{tuple(prop.shape)}")
         nwave, ncol = prop.shape[0], prop.shape[1]
+        if zd is not None:  # the pseudo-spherical beam: checked before the device is touched
+            r = float(self.options.radius())
+            if not (math.isfinite(r) and r > 0.0):
+                raise RuntimeError(f"{who}: zd given: pseudo-spherical geometry needs "
+                                   "DisortOptions.radius (finite, > 0)")
+            if not isinstance(zd, torch.Tensor) or zd.dtype != f64:
+                raise RuntimeError(f"{who}: zd must be a float64 tensor")
+            if zd.dim() not in (1, 2) or zd.shape[-1] != ds.nlyr + 1 or \
+                    (zd.dim() == 2 and zd.shape[0] != ncol):
+                raise RuntimeError(f"{who}: zd must be (nlyr+1,) or (ncol, nlyr+1) = "
+                                   f"({ncol}, {ds.nlyr + 1}), got {tuple(zd.shape)}")
+            if ds.nstr > 16:
+                raise RuntimeError(f"{who}: zd given: pseudo-spherical ray radiances support "
+                                   f"nstr <= 16, got nstr={ds.nstr}")
         for name, t in (("umu", umu), ("phi", phi)):
             if not isinstance(t, torch.Tensor) or t.dtype != f64:
                 raise RuntimeError(f"{who}: {name} must be a float64 tensor")
@@ -503,11 +530,18 @@ class Disort(RTSolver):
                            weight=wts.data_ptr() if band is not None else None,
                            brad=brad.data_ptr() if brad is not None else None)
         stream = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            _context(dev.index).solve_rays(
-                cfg, inp, rays, flux.data_ptr() if flux is not None else None,
+        ptrs = (flux.data_ptr() if flux is not None else None,
                 rad.data_ptr() if rad is not None else None,
                 status.data_ptr() if status is not None else None, stream.cuda_stream)
+        with torch.cuda.device(dev):
+            if zd is not None:
+                z_d = zd.to(dev).contiguous()
+                keep.append(z_d)
+                sph = _lib.HdSphere(radius=float(self.options.radius()), zd=z_d.data_ptr(),
+                                    per_column=int(z_d.dim() == 2))
+                _context(dev.index).solve_rays_spher(cfg, inp, sph, rays, *ptrs)
+            else:
+                _context(dev.index).solve_rays(cfg, inp, rays, *ptrs)
         del keep
         res = brad if band is not None else rad
         return res.to(in_dev) if in_dev.type != "cuda" else res

@@ -1,7 +1,7 @@
 """Throughput of the ray radiances (hd_solve_rays) beside the grid call, in one process.
 
     python scripts/bench_rays.py [--ncol 1000] [--ngpoint 16] [--nstr 16] [--nlyr 80]
-                                 [--steps 5] [--warmup 2] [--out FILE]
+                                 [--steps 5] [--warmup 2] [--out FILE] [--spher [--rounds 5]]
 
 Workload: scripts/bench_rad.py's (the C4 column statistics with a beam, TOA) with its
 8 x 4 directions taken as 32 (cosine, azimuth) pairs, jittered per column (every
@@ -15,6 +15,11 @@ column its own emission angles and azimuths).  One JSON line per leg:
   rays_shared         forward_rays, column 0's 32 pairs shared by every column
   rays_per_column     forward_rays, each column its own 32 pairs
   rays_band           forward_rays_band, per-column pairs, band sum fused, no rad stored
+
+--spher adds one more line, rays_spher_vs_plain: forward_rays(zd=) (the pseudo-spherical
+beam, hd_solve_rays_spher; a Mars-sized radius, levels evenly up to 100 km) beside the plain
+per-column call on the same inputs in the same run, `rounds` alternated rounds of `steps`
+calls each, the median time of each side and their ratio (nstr <= 16).
 
 Times are a host clock around `steps` calls that end in a device synchronise, after
 `warmup` calls of the same leg.  The per-column leg is checked on a subsample against
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--legs", default="grid_8x4,grid_32x32,rays_shared,rays_per_column,rays_band")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--spher", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     from pyharp_amd import Disort, DisortOptions
     if not torch.cuda.is_available():
@@ -73,7 +80,7 @@ def main():
     utau = [0.0]
 
     def module(flags, umu=None, phi=None):
-        op = DisortOptions().flags(flags).nwave(G).ncol(C).user_tau(utau)
+        op = DisortOptions().flags(flags).nwave(G).ncol(C).user_tau(utau).radius(3.39e6)
         if umu is not None:
             op.user_mu(list(map(float, umu))).user_phi(list(map(float, phi)))
         op.ds().nlyr, op.ds().nstr, op.ds().nmom = L, n, n
@@ -123,6 +130,32 @@ def main():
                 err = max(err, np.abs(rad[w, c, 0] - ref).max() / np.abs(ref).max())
             line["max_rel_err_subsample"] = err
         del res
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if a.spher:
+        zd = t(np.linspace(0.0, 1.0e5, L + 1))
+        kw = dict(umu=t(mu_col), phi=t(ph_col))
+        sides = {"plain": lambda: rays.forward_rays(p, b, **kw),
+                 "spher": lambda: rays.forward_rays(p, b, zd=zd, **kw)}
+        ms = {k: [] for k in sides}
+        for fn in sides.values():
+            for _ in range(a.warmup):
+                fn()
+        for _ in range(a.rounds):  # alternated: plain, spher, plain, spher, ...
+            for k, fn in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                torch.cuda.synchronize()
+                ms[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        line = {"leg": "rays_spher_vs_plain", "metric": "ms per call, median of alternated rounds",
+                "plain_ms": med["plain"], "spher_ms": med["spher"],
+                "spher_over_plain_throughput": med["plain"] / med["spher"],
+                "plain_ms_rounds": ms["plain"], "spher_ms_rounds": ms["spher"],
+                "config": {"ncol": C, "ngpoint": G, "nstr": n, "nlyr": L, "ntau": 1,
+                           "directions": 32, "rounds": a.rounds, "steps": a.steps}}
         print(json.dumps(line), flush=True)
         lines.append(line)
     if a.out:
