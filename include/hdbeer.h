@@ -98,6 +98,59 @@ struct hd_beer_rays {
 int hd_beer_rays(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
                  const struct hd_beer_rays *rays, double *rad, int *status, void *stream);
 
+/*
+ * Gradients: the exact adjoint of the three calls above (DESIGN.md section 3d,
+ * "Gradients").  Given the cotangent of a call's result -- dL/d(result) for some scalar
+ * L -- the _bwd calls return dL/d(input) for prop[..][l][0], temf and the boundary
+ * conditions.  cfg and in are those of the forward call.  Not differentiated: the other
+ * slots of prop (never read), umu, the band weights, alpha.
+ *
+ * The cotangent comes in one of two forms; exactly one of per_wave and band + weight is
+ * set, anything else is HD_EINVAL.  m = 2 (nlyr+1) for the fluxes, nray for the rays.
+ */
+typedef struct hd_beer_cot {
+  const double *per_wave; /* DEVICE [nwave][ncol][m]: of flux / rad                   */
+  const double *band;     /* DEVICE [ncol][m]: of bflux / brad; the per-wave          */
+  const double *weight;   /* DEVICE [nwave]     cotangent weight[w] band is not stored */
+} hd_beer_cot;
+
+/*
+ * Optional DEVICE outputs, overwritten; NULL: not wanted.  gtau is dense (no nprop
+ * stride).  gtemf sums over the waves of a column in ascending wave order, carried
+ * through memory from chunk to chunk: bitwise the same at every chunk size, no atomics.
+ * g_x needs in->x; gtemf, g_btemp and g_ttemp need HD_FLAG_PLANCK (HD_EINVAL otherwise;
+ * g_temis is zero without it).  The temperature gradients use
+ *   dB/dT = (4 B - K T^4 (g(v2) - g(v1))) / T,  g(v) = v^4 / (e^v - 1),  v_i = c2 nu_i / T
+ * with the solver's own B: the derivative of the exact band integral, not of the PLKAVG
+ * approximation.
+ */
+typedef struct hd_beer_grads {
+  double *gtau;     /* [nwave][ncol][nlyr]  dL/d prop[..][l][0] */
+  double *gtemf;    /* [ncol][nlyr+1]                           */
+  double *g_albedo; /* [nwave][ncol] each                       */
+  double *g_fbeam;
+  double *g_umu0;
+  double *g_btemp;
+  double *g_ttemp;
+  double *g_temis;
+  double *g_fisot;
+} hd_beer_grads;
+
+/*
+ * Status as the forward calls: a solve they flag HD_STATUS_BAD_INPUT gets the same bit
+ * and NaN gradients (gtemf: NaN in that solve's column), a non-finite gradient sets
+ * HD_STATUS_NONFINITE.  Context, stream, status and capture rules as hd_beer_flux;
+ * scratch is one chunk's Planck levels, dL/dB per level and 2 (nstr/2) nlyr doubles per
+ * solve between the adjoint's two sweeps (16 GB at most).
+ */
+int hd_beer_flux_bwd(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                     const hd_beer_cot *cot, const hd_beer_grads *g, int *status, void *stream);
+
+/* rays: nray, per_column, umu and alpha of the forward call (weight and brad are unused) */
+int hd_beer_rays_bwd(hd_context *ctx, const hd_config *cfg, const hd_inputs *in,
+                     const struct hd_beer_rays *rays, const hd_beer_cot *cot,
+                     const hd_beer_grads *g, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

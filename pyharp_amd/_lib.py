@@ -37,7 +37,8 @@ HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rf
 HD_COORD_WAVELENGTH, HD_COORD_WAVENUMBER = 0, 1
 
 # every symbol include/hdbeer.h declares (the Beer-Lambert solver)
-BEER_EXPORTED = ("hd_beer_flux", "hd_beer_flux_band", "hd_beer_rays")
+BEER_EXPORTED = ("hd_beer_flux", "hd_beer_flux_band", "hd_beer_rays", "hd_beer_flux_bwd",
+                 "hd_beer_rays_bwd")
 
 # every symbol include/hdnc.h declares (netCDF readers, host code)
 NC_EXPORTED = ("hd_nc_open", "hd_nc_close", "hd_nc_dim_len", "hd_nc_var_size",
@@ -88,6 +89,18 @@ class HdRays(ctypes.Structure):
 class HdBeerRays(ctypes.Structure):
     _fields_ = [("nray", ctypes.c_int), ("per_column", ctypes.c_int), ("umu", _dp),
                 ("alpha", ctypes.c_double), ("weight", _dp), ("brad", _dp)]
+
+
+class HdBeerCot(ctypes.Structure):
+    _fields_ = [("per_wave", _dp), ("band", _dp), ("weight", _dp)]
+
+
+BEER_GRADS = ("gtau", "gtemf", "g_albedo", "g_fbeam", "g_umu0", "g_btemp", "g_ttemp", "g_temis",
+              "g_fisot")
+
+
+class HdBeerGrads(ctypes.Structure):
+    _fields_ = [(k, _dp) for k in BEER_GRADS]
 
 
 class HdBand(ctypes.Structure):
@@ -166,6 +179,14 @@ def load(path: str = LIB_PATH):
     lib.hd_beer_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
                                  ctypes.POINTER(HdInputs), ctypes.POINTER(HdBeerRays),
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.hd_beer_flux_bwd.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                     ctypes.POINTER(HdInputs), ctypes.POINTER(HdBeerCot),
+                                     ctypes.POINTER(HdBeerGrads), ctypes.c_void_p,
+                                     ctypes.c_void_p]
+    lib.hd_beer_rays_bwd.argtypes = [ctypes.c_void_p, ctypes.POINTER(HdConfig),
+                                     ctypes.POINTER(HdInputs), ctypes.POINTER(HdBeerRays),
+                                     ctypes.POINTER(HdBeerCot), ctypes.POINTER(HdBeerGrads),
+                                     ctypes.c_void_p, ctypes.c_void_p]
     lib.hd_quadrature.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                   ctypes.POINTER(ctypes.c_double)]
     ci, cd = ctypes.c_int, ctypes.c_double
@@ -357,6 +378,24 @@ class Context:
                                  ctypes.byref(rays), ctypes.c_void_p(rad_ptr or 0),
                                  ctypes.c_void_p(status_ptr or 0),
                                  ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def beer_flux_bwd(self, cfg: HdConfig, inp: HdInputs, cot: HdBeerCot, grads: HdBeerGrads,
+                      status_ptr: int | None, stream_ptr: int | None):
+        """hd_beer_flux_bwd: the gradients of hd_beer_flux / hd_beer_flux_band."""
+        rc = load().hd_beer_flux_bwd(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                     ctypes.byref(cot), ctypes.byref(grads),
+                                     ctypes.c_void_p(status_ptr or 0),
+                                     ctypes.c_void_p(stream_ptr or 0))
+        check(rc, self.handle)
+
+    def beer_rays_bwd(self, cfg: HdConfig, inp: HdInputs, rays: HdBeerRays, cot: HdBeerCot,
+                      grads: HdBeerGrads, status_ptr: int | None, stream_ptr: int | None):
+        """hd_beer_rays_bwd: the gradients of hd_beer_rays."""
+        rc = load().hd_beer_rays_bwd(self.handle, ctypes.byref(cfg), ctypes.byref(inp),
+                                     ctypes.byref(rays), ctypes.byref(cot), ctypes.byref(grads),
+                                     ctypes.c_void_p(status_ptr or 0),
+                                     ctypes.c_void_p(stream_ptr or 0))
         check(rc, self.handle)
 
 

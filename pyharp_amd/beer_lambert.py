@@ -19,6 +19,12 @@ quadrature the fluxes are summed with.  A ray's radiance emerges at the top for
 ``umu > 0`` and at the surface for ``umu < 0``; ``parse_radiation_directions`` supplies
 ``umu`` (its azimuths have no meaning without scattering).
 
+The four methods are differentiable (hd_beer_flux_bwd / hd_beer_rays_bwd, the exact adjoint;
+DESIGN.md section 3d "Gradients") in ``prop[..., 0]``, ``temf`` and the bc entries: with grad
+mode on and one of them requiring grad the result carries a ``grad_fn``; otherwise the call
+is the plain one, bit for bit.  ``umu``, ``weights`` and ``alpha`` are not differentiable,
+and ``out=`` / ``flux=`` / ``rad=`` cannot be combined with an input that requires grad.
+
 CPU tensors are staged with torch copies and the result comes back on the CPU; CUDA
 tensors stay on the device.  There is no CPU path: without a HIP device or the built
 library the calls raise.
@@ -34,6 +40,10 @@ import torch
 from . import _lib
 from .disort import _BC_IGNORED, _BC_KEYS, _arg, _beam_hint, _context
 from .rtsolver import RTSolver
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 class BeerLambertOptions:
@@ -116,6 +126,65 @@ class BeerLambert(RTSolver):
         return self._run("forward_rays_band", prop, bc, temf, status, rad, umu, (weights, out))
 
     # ------------------------------------------------------------------ #
+    def _device_inputs(self, prop, bc, temf, dev):
+        """(prop on dev, the given bc entries on dev as (nwave, ncol), hd_config,
+        hd_inputs) of checked arguments; the tensors back the pointers of hd_inputs"""
+        op = self.options
+        f64 = torch.float64
+        nwave, ncol, nlyr, nprop = prop.shape
+
+        def dev_tensor(x, shape=None):
+            t = torch.as_tensor(x, dtype=f64)
+            if shape is not None and tuple(t.shape) != shape:
+                t = t.expand(shape)
+            return t.to(dev).contiguous()
+
+        keep = [dev_tensor(prop)]
+        bct = {k: dev_tensor(bc[k], (nwave, ncol)) for k in _BC_KEYS if bc.get(k) is not None}
+        tf = wl = wu = None
+        if self.planck:
+            tf = dev_tensor(temf)
+            # cached per device: no host->device copy per call (keeps the calls capturable
+            # into a HIP graph once warmed up)
+            key = (str(dev), tuple(op.wave_lower()), tuple(op.wave_upper()))
+            if self._waves is None or self._waves[0] != key:
+                self._waves = (key, torch.tensor(op.wave_lower(), dtype=f64, device=dev),
+                               torch.tensor(op.wave_upper(), dtype=f64, device=dev))
+            wl, wu = self._waves[1], self._waves[2]
+            keep.append(tf)
+        cfg = _lib.HdConfig(nstr=int(op.nstr()), nmom=0, nlyr=nlyr, nprop=nprop,
+                            flags=_lib.HD_FLAG_LAMBER | _lib.HD_FLAG_ONLYFL |
+                            (_lib.HD_FLAG_PLANCK if self.planck else 0))
+        inp = _lib.HdInputs(nwave=nwave, ncol=ncol, prop=_ptr(keep[0]),
+                            fbeam=_ptr(bct.get("fbeam")), umu0=_ptr(bct.get("umu0")),
+                            albedo=_ptr(bct.get("albedo")), btemp=_ptr(bct.get("btemp")),
+                            ttemp=_ptr(bct.get("ttemp")), temis=_ptr(bct.get("temis")),
+                            fisot=_ptr(bct.get("fisot")), temf=_ptr(tf), wave_lower=_ptr(wl),
+                            wave_upper=_ptr(wu))
+        return keep, bct, cfg, inp
+
+    def _wants_grad(self, who, prop, bc, temf, umu, band, vals):
+        """True if the call is to be differentiated: grad mode on and a differentiable
+        input requires grad.  Raises for what cannot be served."""
+        if not torch.is_grad_enabled():
+            return False
+
+        def req(x):
+            return isinstance(x, torch.Tensor) and x.requires_grad
+
+        if req(umu):
+            raise RuntimeError(f"{who}: umu requires grad, but the view angles are not "
+                               "differentiable (detach umu)")
+        if band is not None and req(band[0]):
+            raise RuntimeError(f"{who}: weights requires grad, but the band weights are not "
+                               "differentiable (detach weights)")
+        if not (req(prop) or (self.planck and req(temf)) or any(req(bc.get(k)) for k in _BC_KEYS)):
+            return False
+        if vals is not None or (band is not None and band[1] is not None):
+            raise RuntimeError(f"{who}: out=, flux= and rad= cannot be combined with an input "
+                               "that requires grad (autograd owns the result)")
+        return True
+
     def _run(self, name, prop, bc, temf, status, vals, umu, band):
         """vals: the caller's per-wave output or None; umu None: fluxes; band: (weights,
         the caller's band output or None) or None."""
@@ -168,43 +237,17 @@ class BeerLambert(RTSolver):
             wts = torch.as_tensor(band[0], dtype=f64).reshape(-1)
             if wts.numel() != nwave:
                 raise RuntimeError(f"{who}: {wts.numel()} weights for {nwave} waves")
+        grad = self._wants_grad(who, prop, bc, temf, umu, band, vals)
         if not torch.cuda.is_available():
             raise RuntimeError(f"{who}: no HIP device available (pyharp_amd has no CPU path)")
+        if grad:
+            return _beer_grad_call(self, name, prop, bc, temf, status, umu, band)
         # --- staging ---
         in_dev = prop.device
         dev = in_dev if in_dev.type == "cuda" else torch.device("cuda", int(op.device()))
-
-        def dev_tensor(x, shape=None):
-            t = torch.as_tensor(x, dtype=f64)
-            if shape is not None and tuple(t.shape) != shape:
-                t = t.expand(shape)
-            return t.to(dev).contiguous()
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
-        keep = [dev_tensor(prop)]
-        bct = {k: dev_tensor(bc[k], (nwave, ncol)) for k in _BC_KEYS if bc.get(k) is not None}
-        tf = wl = wu = None
-        if self.planck:
-            tf = dev_tensor(temf)
-            # cached per device: no host->device copy per call (keeps the calls capturable
-            # into a HIP graph once warmed up)
-            key = (str(dev), tuple(op.wave_lower()), tuple(op.wave_upper()))
-            if self._waves is None or self._waves[0] != key:
-                self._waves = (key, torch.tensor(op.wave_lower(), dtype=f64, device=dev),
-                               torch.tensor(op.wave_upper(), dtype=f64, device=dev))
-            wl, wu = self._waves[1], self._waves[2]
-        cfg = _lib.HdConfig(nstr=int(op.nstr()), nmom=0, nlyr=nlyr, nprop=nprop,
-                            flags=_lib.HD_FLAG_LAMBER | _lib.HD_FLAG_ONLYFL |
-                            (_lib.HD_FLAG_PLANCK if self.planck else 0))
-        inp = _lib.HdInputs(nwave=nwave, ncol=ncol, prop=ptr(keep[0]),
-                            fbeam=ptr(bct.get("fbeam")), umu0=ptr(bct.get("umu0")),
-                            albedo=ptr(bct.get("albedo")), btemp=ptr(bct.get("btemp")),
-                            ttemp=ptr(bct.get("ttemp")), temis=ptr(bct.get("temis")),
-                            fisot=ptr(bct.get("fisot")), temf=ptr(tf), wave_lower=ptr(wl),
-                            wave_upper=ptr(wu))
+        keep, bct, cfg, inp = self._device_inputs(prop, bc, temf, dev)
         tail = (umu.shape[-1],) if rays else (nlyr + 1, 2)
+        ptr = _ptr
 
         def given(t, shape, what):
             if t is not None and (t.device != dev or t.dtype != f64 or not t.is_contiguous()
@@ -251,3 +294,78 @@ class BeerLambert(RTSolver):
         del keep, bct
         res = bout if band is not None else vals
         return res.to(in_dev) if in_dev.type != "cuda" else res
+
+
+# ---------------------------------------------------------------------- #
+# gradients (hd_beer_flux_bwd / hd_beer_rays_bwd)
+# ---------------------------------------------------------------------- #
+def _beer_grad_call(solver, name, prop, bc, temf, status, umu, band):
+    """The call through autograd.  The optical depth enters as the slot-0 view of prop
+    and the bc entries expanded to (nwave, ncol), both by differentiable torch ops: the
+    gradient of a broadcast entry is summed, and that of prop's other slots zeroed, by
+    torch."""
+    nwave, ncol = prop.shape[:2]
+    bcs = [None if bc.get(k) is None else
+           torch.as_tensor(bc[k], dtype=torch.float64).expand(nwave, ncol) for k in _BC_KEYS]
+    tf = torch.as_tensor(temf, dtype=torch.float64) if solver.planck else None
+    wts = None if band is None else torch.as_tensor(band[0], dtype=torch.float64).reshape(-1)
+    return _BeerGrad.apply(solver, name, prop.detach(), status, umu, wts, prop[..., 0], tf, *bcs)
+
+
+class _BeerGrad(torch.autograd.Function):
+    """forward: BeerLambert._run as without autograd; backward: one library call."""
+
+    @staticmethod
+    def forward(ctx, solver, name, prop, status, umu, wts, tau, temf, *bcs):
+        bc = {k: v for k, v in zip(_BC_KEYS, bcs) if v is not None}
+        res = solver._run(name, prop, bc, temf, status, None, umu,
+                          None if wts is None else (wts, None))
+        ctx.solver, ctx.status = solver, status
+        ctx.save_for_backward(prop, umu, wts, temf, *bcs)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        solver = ctx.solver
+        prop, umu, wts, temf, *bcs = ctx.saved_tensors
+        bc = {k: v for k, v in zip(_BC_KEYS, bcs) if v is not None}
+        nwave, ncol, nlyr, _ = prop.shape
+        f64 = torch.float64
+        in_dev = prop.device
+        dev = in_dev if in_dev.type == "cuda" else torch.device("cuda", int(solver.options.device()))
+        keep, bct, cfg, inp = solver._device_inputs(prop, bc, temf, dev)
+        need = dict(zip(("gtau", "gtemf") + tuple("g_" + k for k in _BC_KEYS),
+                        ctx.needs_input_grad[6:]))
+        shapes = {"gtau": (nwave, ncol, nlyr), "gtemf": (ncol, nlyr + 1)}
+        out = {}
+        for k, wanted in need.items():
+            if not wanted or (not solver.planck and k in ("gtemf", "g_btemp", "g_ttemp")):
+                continue  # (without emission the temperatures are not read: no gradient)
+            out[k] = torch.empty(shapes.get(k, (nwave, ncol)), dtype=f64, device=dev)
+        g_dev = gout.to(device=dev, dtype=f64).contiguous()
+        if wts is None:
+            cot = _lib.HdBeerCot(per_wave=g_dev.data_ptr())
+        else:
+            wts_d = wts.to(dev).contiguous()
+            cot = _lib.HdBeerCot(band=g_dev.data_ptr(), weight=wts_d.data_ptr())
+        grads = _lib.HdBeerGrads(**{k: v.data_ptr() for k, v in out.items()})
+        # the bits of the backward go to the caller's status beside the forward's; without
+        # one a solve the forward accepted cannot fail here
+        st = torch.empty(nwave * ncol, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        hctx = _context(dev.index)
+        with torch.cuda.device(dev):
+            if umu is not None:
+                mu_d = umu.to(dev).contiguous()
+                r = _lib.HdBeerRays(nray=umu.shape[-1], per_column=int(umu.dim() == 2),
+                                    umu=mu_d.data_ptr(), alpha=float(solver.options.alpha()))
+                hctx.beer_rays_bwd(cfg, inp, r, cot, grads, st.data_ptr(), stream)
+            else:
+                hctx.beer_flux_bwd(cfg, inp, cot, grads, st.data_ptr(), stream)
+        if ctx.status is not None:
+            ctx.status.view(-1)[:nwave * ncol] |= st
+        del keep, bct
+        res = [out.get(k) for k in need]
+        res = [g if g is None or in_dev.type == "cuda" else g.to(in_dev) for g in res]
+        return (None,) * 6 + tuple(res)

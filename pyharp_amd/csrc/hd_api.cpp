@@ -1710,6 +1710,160 @@ int beer_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in, dou
   return HD_OK;
 }
 
+// the argument checks the two gradient entry points share
+int beer_bwd_check(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                   const hd_beer_cot* cot, const hd_beer_grads* g, const char* who) {
+  const int rc = validate(ctx, cfg, in, nullptr, who, /*out_optional=*/true);
+  if (rc) return rc;
+  if (!cot || !g) return fail(ctx, HD_EINVAL, "%s: null cotangent or gradient set", who);
+  if (cot->per_wave ? (cot->band || cot->weight) : (!cot->band || !cot->weight))
+    return fail(ctx, HD_EINVAL, "%s: the cotangent is either per_wave or band with weight", who);
+  if (!(cfg->flags & HD_FLAG_PLANCK) && (g->gtemf || g->g_btemp || g->g_ttemp))
+    return fail(ctx, HD_EINVAL, "%s: gtemf, g_btemp and g_ttemp need HD_FLAG_PLANCK", who);
+  if ((g->g_albedo && !in->albedo) || (g->g_fbeam && !in->fbeam) || (g->g_umu0 && !in->umu0) ||
+      (g->g_btemp && !in->btemp) || (g->g_ttemp && !in->ttemp) || (g->g_temis && !in->temis) ||
+      (g->g_fisot && !in->fisot))
+    return fail(ctx, HD_EINVAL, "%s: a boundary gradient needs that boundary input", who);
+  return HD_OK;
+}
+
+// rays null: hd_beer_flux_bwd; given: hd_beer_rays_bwd
+int beer_bwd_enqueue(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                     const struct hd_beer_rays* rays, const hd_beer_cot* cot,
+                     const hd_beer_grads* g, int*& status, hipStream_t stream, const char* who) {
+  int rc = HD_OK;
+  const long nsolve = (long)in->nwave * in->ncol;
+  const int nn = cfg->nstr / 2;
+  const int nlyr = cfg->nlyr;
+  const bool planck = (cfg->flags & HD_FLAG_PLANCK) != 0;
+  const hd::BeerGradPlan plan(nn, nlyr, planck, rays != nullptr, nsolve, ctx->chunk);
+  rc = ensure_scratch(ctx, who, plan.total);
+  if (rc) return rc;
+  if (!status && (rc = own_status(ctx, who, (size_t)nsolve, status))) return rc;
+  HD_HIP(ctx, hipMemsetAsync(status, 0, sizeof(int) * nsolve, stream));
+  HD_HIP(ctx, hipMemsetAsync(ctx->anyerr, 0, sizeof(int), stream));
+  if (g->gtemf)
+    HD_HIP(ctx, hipMemsetAsync(g->gtemf, 0, sizeof(double) * in->ncol * (nlyr + 1), stream));
+  if (g->g_temis && !planck)
+    HD_HIP(ctx, hipMemsetAsync(g->g_temis, 0, sizeof(double) * nsolve, stream));
+  double* planck_q = planck ? ctx->scratch + plan.planck : nullptr;
+  double* gb_q = planck ? ctx->scratch + plan.gb : nullptr;
+  double* seed_q = ctx->scratch + plan.seed;
+  const hd::QuadHost& q = quad_host()[nn - 1];
+  const hd::BeerCot kcot{cot->per_wave, cot->band, cot->weight};
+  for (long s0 = 0; s0 < nsolve; s0 += plan.chunk) {
+    const int nsc = (int)std::min(plan.chunk, nsolve - s0);
+    if (planck) {
+      const hd::PlanckArgs pa = planck_args(cfg, in, planck_q, s0, nsc);
+      HD_HIP(ctx, hd::launch_prologue(&pa, nullptr, stream));
+    }
+    hd::BeerBwdArgs a{};
+    a.prop = in->prop;
+    a.fbeam = in->fbeam;
+    a.umu0 = in->umu0;
+    a.albedo = in->albedo;
+    a.fisot = in->fisot;
+    a.planckv = planck_q;
+    a.sweep = ctx->scratch + plan.sweep;
+    a.gb = gb_q;
+    a.gtau = g->gtau;
+    a.g_albedo = g->g_albedo;
+    a.g_fbeam = g->g_fbeam;
+    a.g_umu0 = g->g_umu0;
+    a.g_fisot = g->g_fisot;
+    a.status = status;
+    a.anyerr = ctx->anyerr;
+    a.s0 = s0;
+    a.nsc = nsc;
+    a.ncol = in->ncol;
+    a.nlyr = nlyr;
+    a.nprop = cfg->nprop;
+    for (int i = 0; i < nn; ++i) {
+      a.rmu[i] = 1.0 / q.mu[i];
+      a.wmu[i] = q.w[i] * q.mu[i];
+    }
+    hipError_t e;
+    if (!rays) {
+      a.cot = kcot;
+      e = hd::launch_beer_flux_bwd(nn, a, stream);
+    } else {
+      // the forward's surface intensity into the seed region, then the rays' adjoint
+      // (which replaces it by the seed), then the adjoint of the down pass
+      hd::BeerArgs f{};
+      f.prop = in->prop;
+      f.fbeam = in->fbeam;
+      f.umu0 = in->umu0;
+      f.albedo = in->albedo;
+      f.fisot = in->fisot;
+      f.planckv = planck_q;
+      f.xsurf = seed_q;
+      f.status = status;
+      f.anyerr = ctx->anyerr;
+      f.s0 = s0;
+      f.nsc = nsc;
+      f.nlyr = nlyr;
+      f.nprop = cfg->nprop;
+      for (int i = 0; i < nn; ++i) f.rmu[i] = a.rmu[i], f.wmu[i] = a.wmu[i];
+      e = hd::launch_beer_surface(nn, f, stream);
+      if (e == hipSuccess) {
+        hd::BeerRayBwdArgs r{};
+        r.prop = in->prop;
+        r.albedo = in->albedo;
+        r.fisot = in->fisot;
+        r.planckv = planck_q;
+        r.xsurf = seed_q;
+        r.umu = rays->umu;
+        r.cot = kcot;
+        r.seed = seed_q;
+        r.gb = gb_q;
+        r.gtau = g->gtau;
+        r.g_albedo = g->g_albedo;
+        r.g_fbeam = g->g_fbeam;
+        r.g_umu0 = g->g_umu0;
+        r.g_fisot = g->g_fisot;
+        r.status = status;
+        r.anyerr = ctx->anyerr;
+        r.s0 = s0;
+        r.nsc = nsc;
+        r.ncol = in->ncol;
+        r.nlyr = nlyr;
+        r.nprop = cfg->nprop;
+        r.nray = rays->nray;
+        r.per_column = rays->per_column;
+        r.alpha = rays->alpha;
+        e = hd::launch_beer_rays_bwd(r, stream);
+      }
+      if (e == hipSuccess) {
+        a.seed = seed_q;
+        e = hd::launch_beer_surface_bwd(nn, a, stream);
+      }
+    }
+    if (e == hipSuccess && planck && (g->gtemf || g->g_btemp || g->g_ttemp || g->g_temis)) {
+      hd::BeerPlanckBwdArgs pb{};
+      pb.temf = in->temf;
+      pb.btemp = in->btemp;
+      pb.ttemp = in->ttemp;
+      pb.temis = in->temis;
+      pb.wlo = in->wave_lower;
+      pb.whi = in->wave_upper;
+      pb.planckv = planck_q;
+      pb.gb = gb_q;
+      pb.gtemf = g->gtemf;
+      pb.g_btemp = g->g_btemp;
+      pb.g_ttemp = g->g_ttemp;
+      pb.g_temis = g->g_temis;
+      pb.s0 = s0;
+      pb.nsc = nsc;
+      pb.ncol = in->ncol;
+      pb.nlyr = nlyr;
+      e = hd::launch_beer_planck_bwd(pb, stream);
+    }
+    if (e != hipSuccess)
+      return fail(ctx, HD_EHIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+  }
+  return HD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1760,6 +1914,37 @@ int hd_beer_rays(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
       },
       [&](int*& st, hipStream_t s) {
         return beer_enqueue(ctx, cfg, in, rad, nullptr, rays, st, s, "hd_beer_rays");
+      });
+}
+
+int hd_beer_flux_bwd(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                     const hd_beer_cot* cot, const hd_beer_grads* g, int* status, void* stream) {
+  return solve_entry(
+      ctx, "hd_beer_flux_bwd", in, status, stream,
+      [&] { return beer_bwd_check(ctx, cfg, in, cot, g, "hd_beer_flux_bwd"); },
+      [&](int*& st, hipStream_t s) {
+        return beer_bwd_enqueue(ctx, cfg, in, nullptr, cot, g, st, s, "hd_beer_flux_bwd");
+      });
+}
+
+int hd_beer_rays_bwd(hd_context* ctx, const hd_config* cfg, const hd_inputs* in,
+                     const struct hd_beer_rays* rays, const hd_beer_cot* cot,
+                     const hd_beer_grads* g, int* status, void* stream) {
+  return solve_entry(
+      ctx, "hd_beer_rays_bwd", in, status, stream,
+      [&] {
+        const char* who = "hd_beer_rays_bwd";
+        if (!rays) return fail(ctx, HD_EINVAL, "%s: null ray config", who);
+        if (rays->nray < 1 || !rays->umu)
+          return fail(ctx, HD_EINVAL, "%s: rays need nray >= 1 and umu", who);
+        if (rays->per_column != 0 && rays->per_column != 1)
+          return fail(ctx, HD_EINVAL, "%s: per_column=%d must be 0 or 1", who, rays->per_column);
+        if (!(rays->alpha >= 0.0) || !std::isfinite(rays->alpha))
+          return fail(ctx, HD_EINVAL, "%s: alpha=%g must be finite and >= 0", who, rays->alpha);
+        return beer_bwd_check(ctx, cfg, in, cot, g, who);
+      },
+      [&](int*& st, hipStream_t s) {
+        return beer_bwd_enqueue(ctx, cfg, in, rays, cot, g, st, s, "hd_beer_rays_bwd");
       });
 }
 

@@ -253,4 +253,32 @@ struct BeerPlan {
   }
 };
 
+// ---- scratch of the Beer-Lambert gradients (hd_beer_flux_bwd, hd_beer_rays_bwd) --------
+
+// scratch of one chunk: planck [nlyr+3] | gb [nlyr+3], dL/dB per level (both with Planck
+// only) | sweep [nlyr][2 nn]: the downward intensities and the upward adjoints entering
+// each layer from above, written by the backward kernel's first sweep and read once by
+// its second | seed (rays): the sum of the upward rays' adjoints at the surface.
+// Every region is laid out [..][chunk], the solve fastest.
+struct BeerGradPlan {
+  size_t per_solve;
+  long chunk;
+  size_t planck, gb, sweep, seed;  // offsets (doubles)
+  size_t total;
+
+  BeerGradPlan(int nn, int nlyr, bool planck_, bool rays, long nsolve, long max_chunk) {
+    const size_t npl = planck_ ? (size_t)nlyr + 3 : 0, nsw = 2 * (size_t)nn * nlyr;
+    per_solve = 2 * npl + nsw + (rays ? 1 : 0);
+    const double budget = 16.0 * 1024.0 * 1024.0 * 1024.0 / 8.0;  // doubles
+    chunk = std::min<long>(kBeerChunk, std::max<long>(1, (long)(budget / (double)per_solve)));
+    if (max_chunk > 0) chunk = std::min(chunk, max_chunk);
+    chunk = std::max<long>(1, std::min(chunk, nsolve));
+    planck = 0;
+    gb = npl * chunk;
+    sweep = 2 * npl * chunk;
+    seed = sweep + nsw * chunk;
+    total = per_solve * (size_t)chunk;
+  }
+};
+
 }  // namespace hd
