@@ -116,6 +116,79 @@ int hd_rfm_attenuate(const hd_rfm_table *t, const double *conc, int ncol, int nl
                      int nspecies, const double *pres, const double *temp, double *out,
                      void *stream);
 
+/* ---- Gradients of the optics ----------------------------------------------------
+ * The adjoints of the four optics calls above (hd_harp_grad.hip): given the cotangent
+ * of a call's output they return the cotangents of its differentiable inputs.  All
+ * pointers are DEVICE pointers, the calls are stream-ordered, and the return codes and
+ * argument checks are the forward's (a NULL cotangent with work to do is HD_EINVAL;
+ * nothing is launched on an error).  An output pointer that is NULL is "not wanted":
+ * its work is skipped and the other outputs keep their bits.  gconc is written whole,
+ * [ncol][nlyr][nspecies], with zeros in the species no attenuator reads.  The spectral
+ * coordinate and the tables are not differentiated.
+ *
+ * Definition.  Each call returns the derivative of the mathematical function along the
+ * branch the forward took, not of the forward's rounding:
+ *
+ *   interpolation (locate / index pair / two-point formula, on every axis):
+ *     inside a cell the slope is (v2 - v1)/(x2 - x1);
+ *     where the forward clamps (i1 == i2: below or above the table, or exactly on the
+ *     last knot) the slope is 0;
+ *     exactly on an inner knot the slope is that of the cell locate returns, the one to
+ *     the right.
+ *   hd_rfm_attenuate: out = 1e-3 exp(v) c with v = interpn(kdata; wave_w, x_p = ln p,
+ *     x_t = T - T_ref(ln p)):
+ *       d/dc = 1e-3 exp(v)
+ *       d/dT = out dv/dx_t
+ *       d/dp = out (dv/dx_p - dv/dx_t T_ref'(ln p)) / p   (x_t depends on p through T_ref)
+ *     exp(v) is recomputed from the inputs, never a saved output over c: d/dc is right
+ *     at c = 0.  The index pairs are the forward's own (T_ref and the anomaly are formed
+ *     in the forward's arithmetic).
+ *   hd_attenuate: d/dc = k (g[0] + ssa g[1]).
+ *   hd_band_optics: tau = dz ext, ssa = sca/ext.  gdz comes from tau only (the forward's
+ *     (sca dz)/(ext dz) does not depend on dz).  A layer with ext == 0, where the forward
+ *     sets ssa = 0, gets nothing through ssa and still k_a dz g_tau through tau.
+ *   hd_band_loop_optics: ext = ext0 + sum_a k_a c_a, sca, m_l, P_1 = sca/(ext + 1e-10),
+ *     P_{1+l} = m_l/(sca + 1e-10), P_0 = ext dz differentiated as written, both 1e-10
+ *     kept.  gext0 [nwave][ncol][nlyr] = dL/dext per element.
+ *   Attenuators that read the same species: each attenuator's d/dc_a is summed over the
+ *     waves on its own (below); the sums of one species then add in array order, from 0.
+ *
+ * Summation order.  Every gradient but gext0 is a sum over the wave axis,
+ * [nwave][ncol][nlyr] -> [ncol][nlyr].  Its order is a function of nwave alone -- never
+ * of ncol, nlyr, the launch grid or the route the launcher takes:
+ *   the waves are split into blocks of WB = 32 consecutive waves (the last one shorter);
+ *   a block's sum starts from 0 and adds its waves' terms in ascending wave order;
+ *   the total starts from 0 and adds the block sums in ascending block order.
+ * With many (col, lyr) a lane owns one and walks the blocks itself; with few, the blocks
+ * are spread over the grid, written to stream-ordered scratch and added by a second
+ * kernel.  Both routes give the same bits; there are no atomics.  For hd_rfm_attenuate
+ * the term of gpres carries its 1/p (the sum is not scaled afterwards). */
+
+/* gout [nwave][ncol][nlyr][2] -> gconc [ncol][nlyr][nspecies] */
+int hd_attenuate_bwd(const hd_attenuator *att, const double *coord, int coord_kind, int nwave,
+                     const double *conc, int ncol, int nlyr, int nspecies,
+                     const double *gout, double *gconc, void *stream);
+
+/* gprop [nwave][ncol][nlyr][nprop] -> gconc, gdz [ncol][nlyr] */
+int hd_band_optics_bwd(const hd_attenuator *atts, int natt, const double *coord, int coord_kind,
+                       int nwave, const double *conc, int ncol, int nlyr, int nspecies,
+                       const double *dz, int nprop, const double *gprop,
+                       double *gconc, double *gdz, void *stream);
+
+/* gprop [nwave][ncol][nlyr][2+nmom] -> gconc, gdz [ncol][nlyr], gext0 [nwave][ncol][nlyr]
+ * (ext0 NULL as in the forward; gext0 may be asked for all the same) */
+int hd_band_loop_optics_bwd(const hd_band_attenuator *atts, int natt, const double *ext0,
+                            const double *coord, int coord_kind, int nwave, const double *conc,
+                            int ncol, int nlyr, int nspecies, const double *dz, int nmom,
+                            const double *gprop, double *gconc, double *gdz,
+                            double *gext0, void *stream);
+
+/* gout [nwave][ncol][nlyr] -> gconc, gpres and gtemp [ncol][nlyr], from one pass */
+int hd_rfm_attenuate_bwd(const hd_rfm_table *t, const double *conc, int ncol, int nlyr,
+                         int nspecies, const double *pres, const double *temp,
+                         const double *gout,
+                         double *gconc, double *gpres, double *gtemp, void *stream);
+
 /* bflux [ncol][nlev][2] = sum_w weight[w] flux[w][ncol][nlev][2] (fixed order) */
 int hd_band_flux(const double *flux, const double *weight, int nwave, int ncol, int nlev,
                  double *bflux, void *stream);

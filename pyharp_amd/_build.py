@@ -14,8 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhdisort.so")
 SOURCES = ["hd_kernels.hip", "hd_team_mfma.hip", "hd_rad.hip", "hd_harp.hip",
-           "hd_api.cpp", "hd_ncread.cpp", "hd_rad_wide.hip", "hd_beer.hip", "hd_rad_spher.hip"]
-HEADERS = ["hd_device.hpp", "hd_kernels.hpp", "hd_plan.hpp", "hd_beer.hpp", "hd_rad.hpp", "hd_rad_layout.hpp", "hd_rad_lane.hpp", "hd_team_prims.hpp",
+           "hd_api.cpp", "hd_ncread.cpp", "hd_rad_wide.hip", "hd_beer.hip", "hd_rad_spher.hip",
+           "hd_harp_grad.hip"]
+HEADERS = ["hd_device.hpp", "hd_harp_interp.hpp", "hd_kernels.hpp", "hd_plan.hpp", "hd_beer.hpp", "hd_rad.hpp", "hd_rad_layout.hpp", "hd_rad_lane.hpp", "hd_team_prims.hpp",
            os.path.join("..", "..", "include", "hdisort.h"),
            os.path.join("..", "..", "include", "hdharp.h"),
            os.path.join("..", "..", "include", "hdbeer.h"),

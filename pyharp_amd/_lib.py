@@ -33,7 +33,8 @@ EXPORTED = ("hd_version", "hd_last_error", "hd_context_create", "hd_context_dest
 # every symbol include/hdharp.h declares (harp-side steps around the solve)
 HARP_EXPORTED = ("hd_attenuate", "hd_band_optics", "hd_band_loop_optics", "hd_rfm_attenuate",
                  "hd_band_flux", "hd_band_sum", "hd_heating_rate",
-                 "hd_spherical_flux_correction")
+                 "hd_spherical_flux_correction", "hd_attenuate_bwd", "hd_band_optics_bwd",
+                 "hd_band_loop_optics_bwd", "hd_rfm_attenuate_bwd")
 HD_COORD_WAVELENGTH, HD_COORD_WAVENUMBER = 0, 1
 
 # every symbol include/hdbeer.h declares (the Beer-Lambert solver)
@@ -198,6 +199,15 @@ def load(path: str = LIB_PATH):
                                         _dp, ci, ci, ci, _dp, ci, _dp, _dp]
     lib.hd_rfm_attenuate.argtypes = [ctypes.POINTER(HdRfmTable), _dp, ci, ci, ci, _dp, _dp, _dp,
                                      _dp]
+    lib.hd_attenuate_bwd.argtypes = [ctypes.POINTER(HdAttenuator), _dp, ci, ci, _dp, ci, ci, ci,
+                                     _dp, _dp, _dp]
+    lib.hd_band_optics_bwd.argtypes = [ctypes.POINTER(HdAttenuator), ci, _dp, ci, ci, _dp, ci, ci,
+                                       ci, _dp, ci, _dp, _dp, _dp, _dp]
+    lib.hd_band_loop_optics_bwd.argtypes = [ctypes.POINTER(HdBandAttenuator), ci, _dp, _dp, ci,
+                                            ci, _dp, ci, ci, ci, _dp, ci, _dp, _dp, _dp, _dp,
+                                            _dp]
+    lib.hd_rfm_attenuate_bwd.argtypes = [ctypes.POINTER(HdRfmTable), _dp, ci, ci, ci, _dp, _dp,
+                                         _dp, _dp, _dp, _dp, _dp]
     lib.hd_band_flux.argtypes = [_dp, _dp, ci, ci, ci, _dp, _dp]
     lib.hd_band_sum.argtypes = [_dp, _dp, ci, ctypes.c_long, _dp, _dp]
     lib.hd_heating_rate.argtypes = [_dp, _dp, _dp, cd, ci, ci, _dp, _dp]

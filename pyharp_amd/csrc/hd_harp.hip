@@ -34,6 +34,8 @@
 
 #pragma clang fp contract(off)
 
+#include "hd_harp_interp.hpp"  // locate_dev, bracket, lerp_ref (shared with hd_harp_grad.hip)
+
 namespace hd {
 namespace {
 
@@ -49,23 +51,6 @@ struct AttTables {
   int natt;
   int nv;  // values per (attenuator, wave) in coef: 2 {k, ssa} or 3 {k, ssa, g}
 };
-
-// zero-offset j with xx[j] <= x < xx[j+1] for ascending or descending xx,
-// -1 below / n-1 above the range (Numerical Recipes locate, as locate.h)
-__device__ int locate_dev(const double* xx, double x, int n) {
-  int jl = 0, ju = n + 1;  // unit offsets
-  const bool ascnd = xx[n - 1] >= xx[0];
-  while (ju - jl > 1) {
-    const int jm = (ju + jl) >> 1;
-    if ((x >= xx[jm - 1]) == ascnd) jl = jm;
-    else ju = jm;
-  }
-  int j;
-  if (x == xx[0]) j = 1;
-  else if (x == xx[n - 1]) j = n;
-  else j = jl;
-  return j - 1;
-}
 
 // coef[a][w] = {k(lambda_w), ssa(lambda_w)[, g(lambda_w)]}
 __global__ __launch_bounds__(256) void hd_att_coef_kernel(AttTables T, const double* coord,
@@ -267,24 +252,6 @@ int launched(const char* what) {
 }  // namespace
 
 // ---- RFM tables (harp::RFMImpl, src/opacity/rfm.cpp:122-225) ----------------
-// interpn.h's index pair and arithmetic on one axis
-__device__ __forceinline__ void bracket(const double* ax, int n, double x, int& i1, int& i2) {
-  i1 = locate_dev(ax, x, n);
-  if (i1 == -1) {
-    i1 = 0;
-    i2 = 0;
-  } else if (i1 == n - 1) {
-    i2 = n - 1;
-  } else {
-    i2 = i1 + 1;
-  }
-}
-__device__ __forceinline__ double lerp_ref(const double* ax, int i1, int i2, double x, double v1,
-                                           double v2) {
-  const double x1 = ax[i1], x2 = ax[i2];
-  return x2 != x1 ? ((x - x1) * v2 + (x2 - x) * v1) / (x2 - x1) : (v1 + v2) / 2.;
-}
-
 // per (col, lyr): ln p and the temperature anomaly T - T_ref(ln p)  [get_reftemp]
 __global__ __launch_bounds__(256) void hd_rfm_state_kernel(hd_rfm_table t, const double* pres,
                                                            const double* temp, long n,

@@ -22,6 +22,12 @@ Mirrors the two attenuators pyharp's SW example builds its optics from
 The arithmetic runs in libhdisort.so (include/hdharp.h); tables are read on
 the host (file parsing is not on the device path).  There is no CPU compute
 path: forward() on a machine without a HIP device raises.
+
+The four optics calls are differentiable (hd_*_bwd, include/hdharp.h "Gradients of the
+optics"): with grad mode on and conc, pres, temp, dz or ext0 requiring grad they go
+through a ``torch.autograd.Function`` whose forward is the call below unchanged and whose
+backward is one library call.  The spectral coordinate and the tables are not
+differentiable.
 """
 
 from __future__ import annotations
@@ -131,6 +137,171 @@ def _f64(x, dev) -> torch.Tensor:
     return torch.as_tensor(x, dtype=torch.float64).to(dev).contiguous()
 
 
+def _req(x) -> bool:
+    return isinstance(x, torch.Tensor) and x.requires_grad
+
+
+def _wants_grad(who, coord_name, coord, inputs, out=None) -> bool:
+    """True if the call is to be differentiated: grad mode on and a differentiable
+    input requires grad.  Raises for what cannot be served."""
+    if not torch.is_grad_enabled():
+        return False
+    if _req(coord):
+        raise RuntimeError(f"{who}: {coord_name} requires grad, but the spectral coordinate is "
+                           f"not differentiable (detach {coord_name})")
+    if not any(_req(x) for x in inputs):
+        return False
+    if out is not None:
+        raise RuntimeError(f"{who}: out= cannot be combined with an input that requires grad "
+                           "(autograd owns the result)")
+    return True
+
+
+def _as_f64(x) -> torch.Tensor:
+    """float64 by a differentiable op (the caller's tensor itself when it already is)"""
+    return torch.as_tensor(x).to(torch.float64)
+
+
+def _layer_dz(dz, ncol, nlyr) -> torch.Tensor:
+    d = torch.as_tensor(dz, dtype=torch.float64)
+    if d.dim() == 2 and d.shape == (nlyr, 1):
+        d = d[:, 0]
+    return d.expand(ncol, nlyr)
+
+
+def _grad_out(ctx, i, shape, dev):
+    return torch.empty(shape, dtype=torch.float64, device=dev) if ctx.needs_input_grad[i] else None
+
+
+def _back(g, like):
+    """a gradient on the device of the input it belongs to"""
+    return g if g is None or like.device == g.device else g.to(like.device)
+
+
+class _AttenuateGrad(torch.autograd.Function):
+    """forward: _TableAttenuator.forward as without autograd; backward: hd_attenuate_bwd."""
+
+    @staticmethod
+    def forward(ctx, att, conc, coord, kind):
+        ctx.att, ctx.kind = att, kind
+        ctx.save_for_backward(conc, coord)
+        return att.forward(conc, {("wavelength", "wavenumber")[kind]: coord})
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        conc, coord = ctx.saved_tensors
+        dev = _device(conc, coord)
+        c, x = _f64(conc, dev), _f64(coord, dev).reshape(-1)
+        ncol, nlyr, nsp = c.shape
+        g = _f64(gout, dev)
+        gconc = torch.empty_like(c)
+        att = ctx.att.hd_struct(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hd_attenuate_bwd(
+                ctypes.byref(att), x.data_ptr(), ctx.kind, x.numel(), c.data_ptr(), ncol, nlyr,
+                nsp, g.data_ptr(), gconc.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return None, _back(gconc, conc), None, None
+
+
+class _BandOpticsGrad(torch.autograd.Function):
+    """forward: band_optics as without autograd; backward: hd_band_optics_bwd."""
+
+    @staticmethod
+    def forward(ctx, attenuators, conc, dz, coord, kind, nprop):
+        ctx.attenuators, ctx.kind, ctx.nprop = attenuators, kind, nprop
+        ctx.save_for_backward(conc, dz, coord)
+        return band_optics(attenuators, conc, dz, {("wavelength", "wavenumber")[kind]: coord},
+                           nprop)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gprop):
+        conc, dz, coord = ctx.saved_tensors
+        dev = gprop.device
+        c, d, x = _f64(conc, dev), _f64(dz, dev), _f64(coord, dev).reshape(-1)
+        ncol, nlyr, nsp = c.shape
+        g = _f64(gprop, dev)
+        gconc, gdz = _grad_out(ctx, 1, c.shape, dev), _grad_out(ctx, 2, (ncol, nlyr), dev)
+        n = len(ctx.attenuators)
+        atts = (_lib.HdAttenuator * n)(*[a.hd_struct(dev) for a in ctx.attenuators])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hd_band_optics_bwd(
+                atts, n, x.data_ptr(), ctx.kind, x.numel(), c.data_ptr(), ncol, nlyr, nsp,
+                d.data_ptr(), ctx.nprop, g.data_ptr(), _ptr(gconc), _ptr(gdz),
+                torch.cuda.current_stream(dev).cuda_stream))
+        return None, _back(gconc, conc), _back(gdz, dz), None, None, None
+
+
+class _BandLoopGrad(torch.autograd.Function):
+    """forward: band_loop_optics as without autograd; backward: hd_band_loop_optics_bwd."""
+
+    @staticmethod
+    def forward(ctx, attenuators, conc, dz, ext0, coord, kind, nmom):
+        ctx.attenuators, ctx.kind, ctx.nmom = attenuators, kind, nmom
+        ctx.save_for_backward(conc, dz, ext0, coord)
+        return band_loop_optics(attenuators, conc, dz,
+                                {("wavelength", "wavenumber")[kind]: coord}, nmom, ext0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gprop):
+        conc, dz, ext0, coord = ctx.saved_tensors
+        dev = gprop.device
+        c, d, x = _f64(conc, dev), _f64(dz, dev), _f64(coord, dev).reshape(-1)
+        e0 = None if ext0 is None else _f64(ext0, dev)
+        ncol, nlyr, nsp = c.shape
+        nwave = x.numel()
+        g = _f64(gprop, dev)
+        gconc, gdz = _grad_out(ctx, 1, c.shape, dev), _grad_out(ctx, 2, (ncol, nlyr), dev)
+        gext0 = None if ext0 is None else _grad_out(ctx, 3, tuple(ext0.shape), dev)
+        structs = []
+        for a in ctx.attenuators:
+            t = a._tables(dev)[3]
+            structs.append(_lib.HdBandAttenuator(table=a.hd_struct(dev),
+                                                 gasym=None if t is None else t.data_ptr()))
+        atts = (_lib.HdBandAttenuator * len(structs))(*structs)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hd_band_loop_optics_bwd(
+                atts, len(structs), _ptr(e0), x.data_ptr(), ctx.kind, nwave, c.data_ptr(), ncol,
+                nlyr, nsp, d.data_ptr(), ctx.nmom, g.data_ptr(), _ptr(gconc), _ptr(gdz),
+                _ptr(gext0), torch.cuda.current_stream(dev).cuda_stream))
+        return (None, _back(gconc, conc), _back(gdz, dz),
+                None if gext0 is None else _back(gext0, ext0), None, None, None)
+
+
+class _RfmGrad(torch.autograd.Function):
+    """forward: RFM.forward as without autograd; backward: hd_rfm_attenuate_bwd."""
+
+    @staticmethod
+    def forward(ctx, rfm, conc, pres, temp):
+        ctx.rfm = rfm
+        ctx.save_for_backward(conc, pres, temp)
+        return rfm.forward(conc, {"pres": pres, "temp": temp})
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        conc, pres, temp = ctx.saved_tensors
+        dev = _device(conc, pres, temp)
+        c, p, t = _f64(conc, dev), _f64(pres, dev), _f64(temp, dev)
+        ncol, nlyr, nsp = c.shape
+        g = _f64(gout, dev)
+        gconc = _grad_out(ctx, 1, c.shape, dev)
+        gpres, gtemp = _grad_out(ctx, 2, (ncol, nlyr), dev), _grad_out(ctx, 3, (ncol, nlyr), dev)
+        tab = ctx.rfm.hd_struct(dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().hd_rfm_attenuate_bwd(
+                ctypes.byref(tab), c.data_ptr(), ncol, nlyr, nsp, p.data_ptr(), t.data_ptr(),
+                g.data_ptr(), _ptr(gconc), _ptr(gpres), _ptr(gtemp),
+                torch.cuda.current_stream(dev).cuda_stream))
+        return None, _back(gconc, conc), _back(gpres, pres), _back(gtemp, temp)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _TableAttenuator:
     """Common body of S8FullerImpl / H2SO4SimpleImpl (identical but for the type)."""
 
@@ -191,6 +362,11 @@ class _TableAttenuator:
 
     def forward(self, conc: torch.Tensor, kwargs: Dict[str, torch.Tensor]) -> torch.Tensor:
         coord, kind = _coord(kwargs)
+        if _wants_grad(type(self).__name__ + ".forward", ("wavelength", "wavenumber")[kind],
+                       coord, (conc,)):
+            if conc.dim() != 3:
+                raise RuntimeError("conc must be (ncol, nlyr, nspecies)")
+            return _AttenuateGrad.apply(self, _as_f64(conc), torch.as_tensor(coord), kind)
         dev = _device(conc, coord)
         c = _f64(conc, dev)
         if c.dim() != 3:
@@ -237,8 +413,13 @@ def band_optics(attenuators: Sequence[_TableAttenuator], conc: torch.Tensor, dz:
     assembly (``prop = s8(conc) + h2so4(conc); prop *= dz; prop[...,1] /= prop[...,0]``,
     examples/amars_sw.cpp:261-271) in one kernel.  dz: (nlyr,), (nlyr, 1) or
     (ncol, nlyr) [m].  Layers without extinction get ssa = 0 (the reference's
-    0/0 would be NaN)."""
+    0/0 would be NaN).  Differentiable in conc and dz (hd_band_optics_bwd)."""
     coord, kind = _coord(kwargs)
+    if _wants_grad("band_optics", ("wavelength", "wavenumber")[kind], coord, (conc, dz), out):
+        ncol, nlyr, _ = conc.shape
+        return _BandOpticsGrad.apply(tuple(attenuators), _as_f64(conc),
+                                     _layer_dz(dz, ncol, nlyr), torch.as_tensor(coord), kind,
+                                     int(nprop))
     dev = _device(conc, coord, dz)
     c = _f64(conc, dev)
     ncol, nlyr, nsp = c.shape
@@ -270,8 +451,20 @@ def band_loop_optics(attenuators: Sequence[_TableAttenuator], conc: torch.Tensor
     sum_a g_a^l ssa_a k_a c_a / (sum_a ssa_a k_a c_a + 1e-10) over the attenuators
     with an asymmetry table, tau = ext dz -- in the reference's operation order.
     ext0: (nwave, ncol, nlyr[, 1]) extinction of attenuators without ssa (an RFM
-    module's forward), added first."""
+    module's forward), added first.  Differentiable in conc, dz and ext0
+    (hd_band_loop_optics_bwd)."""
     coord, kind = _coord(kwargs)
+    if _wants_grad("band_loop_optics", ("wavelength", "wavenumber")[kind], coord,
+                   (conc, dz, ext0), out):
+        ncol, nlyr, _ = conc.shape
+        nwave = torch.as_tensor(coord).numel()
+        e0 = None
+        if ext0 is not None:
+            if ext0.numel() != nwave * ncol * nlyr:
+                raise RuntimeError(f"band_loop_optics: ext0 must hold {(nwave, ncol, nlyr)}")
+            e0 = _as_f64(ext0).reshape(nwave, ncol, nlyr)
+        return _BandLoopGrad.apply(tuple(attenuators), _as_f64(conc), _layer_dz(dz, ncol, nlyr),
+                                   e0, torch.as_tensor(coord), kind, int(nmom))
     dev = _device(conc, coord, dz)
     c = _f64(conc, dev)
     ncol, nlyr, nsp = c.shape
@@ -317,7 +510,8 @@ class RFM:
     builds the same module from in-memory tables.  ``forward(conc, kwargs)``
     with ``kwargs["pres"]`` [Pa] and ``kwargs["temp"]`` [K] (ncol, nlyr) returns
     (nwave, ncol, nlyr, 1) = 1e-3 exp(k) conc [1/m], interpolated on the device
-    (include/hdharp.h hd_rfm_attenuate).
+    (include/hdharp.h hd_rfm_attenuate).  Differentiable in conc, pres and temp
+    (hd_rfm_attenuate_bwd).
     """
 
     IPR, ITM = 0, 1
@@ -390,6 +584,13 @@ class RFM:
             raise RuntimeError("pres is required in kwargs")
         if "temp" not in kwargs:
             raise RuntimeError("temp is required in kwargs")
+        if _wants_grad("RFM.forward", "", None, (conc, kwargs["pres"], kwargs["temp"])):
+            if conc.dim() != 3:
+                raise RuntimeError("conc must be (ncol, nlyr, nspecies)")
+            ncol, nlyr, _ = conc.shape
+            return _RfmGrad.apply(self, _as_f64(conc),
+                                  _as_f64(kwargs["pres"]).expand(ncol, nlyr),
+                                  _as_f64(kwargs["temp"]).expand(ncol, nlyr))
         dev = _device(conc, kwargs["pres"], kwargs["temp"])
         c = _f64(conc, dev)
         if c.dim() != 3:
